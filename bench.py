@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- agent-days/s of the MI355X-native day step, with roofline and CPU baseline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--agents A] [--no-cpu] [--no-sizes] [--no-ensemble]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--agents A] [--no-cpu] [--no-sizes] [--no-ensemble] [--dump-outputs DIR]
 
 A "step" is one simulated day (Context.iterate of the reference, cythonsim/main.pyx:2011-2018)
 over the whole population.  At N=1 the workload is BASELINE.json configs[1]: the HUS population
@@ -38,6 +38,10 @@ Objects on the line:
                  on one host core over THE SAME day window (W untimed, K timed days), repeated over seeds
                  until about 10 s of timed work; `all_cores`: one simulation per core, all started together,
                  over the same window (--cpu-all-cores-days n: the first n days instead, labelled).
+
+`--dump-outputs DIR` writes what the timed run computed -- the history its caller receives and the counters the last timed day
+left -- to DIR as float64 .npy files (dump_outputs).  The inputs depend on the arguments alone (--seed, default 0), so two builds
+of the project run with the same arguments can be compared file for file.
 """
 import argparse
 import copy
@@ -106,7 +110,8 @@ def stride_for(steps, time_every):
     return 4 if steps < 16 else 8 if steps < 64 else 16
 
 
-def run_gpu(variables, ages, seed, steps, warmup, device, dist=None, preheat=0, stride=16, preheat_runs=2, attribution='mirror', day_only=False):
+def run_gpu(variables, ages, seed, steps, warmup, device, dist=None, preheat=0, stride=16, preheat_runs=2, attribution='mirror', day_only=False,
+            keep_outputs=False):
     import numpy as np
     import torch
     from reina_model_amd import engine as eng
@@ -156,6 +161,8 @@ def run_gpu(variables, ages, seed, steps, warmup, device, dist=None, preheat=0, 
         gc.enable()
     prof = ctx.engine.profile_read_kernels()
     ctx.engine.profile_enable(False)
+    # (read after the clock stopped: the counter block the last timed day left, summed over the shards -- a collective, every rank reads)
+    final = ctx._read_counters_global() if keep_outputs else None
     A = eng.MAX_AGES
 
     def tot(name):
@@ -183,7 +190,28 @@ def run_gpu(variables, ages, seed, steps, warmup, device, dist=None, preheat=0, 
     rccl_world = None
     if comm is not None and getattr(comm, 'direct', None) is not None:
         rccl_world = comm.direct.count()
-    return dict(dt=t1 - t0, prof=prof, stats=stats, n_local=ctx.total_people, rccl_world=rccl_world, exchange_fill=ctx.exchange_fill())
+    out = dict(dt=t1 - t0, prof=prof, stats=stats, n_local=ctx.total_people, rccl_world=rccl_world, exchange_fill=ctx.exchange_fill())
+    if keep_outputs:
+        out['outputs'] = dict(history=hist, final_counters=final, first_day=warmup)
+    return out
+
+
+DUMP_LIMIT_BYTES = 64_000_000   # all files of a dump together, .npy headers included
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: what the timed ctx.run(steps) handed its caller -- history[steps, COUNTER_WORDS], row d = the counters before
+    day first_day + d ran -- and the counter block the last timed day left behind, as float64 .npy files (the int32 counters are exact
+    in float64).  The whole history always fits the cap: the engine simulates fewer than MAX_DAYS = 4096 days, about 60 MB of rows."""
+    import numpy as np
+    hist = np.asarray(outputs['history'], dtype=np.float64)
+    final = np.asarray(outputs['final_counters'], dtype=np.float64)
+    days = np.arange(hist.shape[0], dtype=np.float64) + outputs['first_day']
+    assert hist.nbytes + days.nbytes + final.nbytes + 3 * 1024 <= DUMP_LIMIT_BYTES, hist.shape
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'history.npy'), hist)
+    np.save(os.path.join(path, 'history_days.npy'), days)
+    np.save(os.path.join(path, 'final_counters.npy'), final)
 
 
 def lib_sha256():
@@ -707,7 +735,11 @@ def main():
                     help='each kind of kernel carries HIP event timestamps on every k-th day (0: 4 / 8 / 16 by run length)')
     ap.add_argument('--preheat-days', type=int, default=365,
                     help='days of a throw-away simulation run before the measured one (GPU clocks, one-time costs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed run computed (history.npy, history_days.npy, final_counters.npy) to DIR')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(a.gpus))
@@ -778,7 +810,7 @@ def main():
         os.environ['REINA_COUNT_ROW_CACHE'] = '0'
     try:
         res = run_gpu(v, ages, a.seed, a.steps, a.warmup, device, dist, preheat=a.preheat_days, stride=stride, attribution=a.attribution,
-                      day_only=cold_headline)
+                      day_only=cold_headline, keep_outputs=a.dump_outputs is not None)
     finally:
         os.environ.pop('REINA_COUNT_ROW_CACHE', None)
     res['dt'] = max_over_ranks(res['dt'])
@@ -964,6 +996,8 @@ def main():
             'timed_region_s': round(res['dt'], 6), 'process_wall_s': round(time.perf_counter() - t_process, 2),
             'note': 'the process also builds contexts, runs untimed preheat simulations, the full_scenario / ensemble '
                     'configurations and the CPU baselines; value = agents x steps / timed_region_s'}
+        if a.dump_outputs is not None:
+            dump_outputs(a.dump_outputs, res['outputs'])
         write_detail(out)
         print(json.dumps(compact_line(out), separators=(',', ':')), flush=True)
     if world > 1:

@@ -120,7 +120,8 @@ def test_recorded_line_of_this_round_parses_and_fits():
 def test_a_multi_gpu_line_fits_too():
     """`bench.py --gpus N` adds `large`, `strong` (with the other attribution mode beside it) and a distributed `ensemble` to the object:
     the digest keeps them under the same cap (verdict r05 item 9: "keep the --gpus 8 line under item 1's size cap too")"""
-    full = json.load(open(os.path.join(ROOT, 'profiles', 'bench_detail.json')))
+    # (the full object of round 6's recorded run; profiles/bench_detail.json is rewritten by every bench.py run)
+    full = json.load(open(os.path.join(ROOT, 'profiles', 'r06_bench_detail.json')))
     fs = full['full_scenario']['100000000']
     out = {k: v for k, v in full.items() if k not in ('full_scenario', 'cpu_baseline', 'value_warm', 'ms_per_step_warm', 'headline_is')}
     out['n_gpus'] = 8
@@ -140,3 +141,23 @@ def test_a_multi_gpu_line_fits_too():
     assert line['n_gpus'] == 8 and line['config']['attribution'] == 'mirror' and line['config']['rccl_world'] == 8
     assert line['large']['value'] == 1.0e12 and line['large']['kernel_us']['collective'] == 31.0 and line['large']['roofline']['frac'] > 0
     assert line['strong']['exact']['value'] == 6.0e11 and line['strong']['scaling'] == 'strong' and 'cpu_baseline' not in line
+
+
+def test_dump_outputs_writes_float64_arrays_under_the_cap(tmp_path):
+    """`bench.py --dump-outputs DIR`: the timed run's history and the counters of its last day as float64 .npy files, at most
+    64 MB in all even for the longest run the engine allows (MAX_DAYS - 1 timed days)"""
+    import numpy as np
+    from reina_model_amd import engine as eng
+    W = eng.COUNTER_WORDS
+    hist = (np.arange(20 * W, dtype=np.int64) % 2**31).astype(np.int32).reshape(20, W)
+    final = np.arange(W, dtype=np.int32) - 7
+    bench.dump_outputs(str(tmp_path / 'a'), dict(history=hist, final_counters=final, first_day=5))
+    h = np.load(tmp_path / 'a' / 'history.npy')
+    assert h.dtype == np.float64 and np.array_equal(h, hist)
+    assert np.array_equal(np.load(tmp_path / 'a' / 'history_days.npy'), np.arange(5, 25))
+    f = np.load(tmp_path / 'a' / 'final_counters.npy')
+    assert f.dtype == np.float64 and np.array_equal(f, final)
+    longest = np.ones((eng.MAX_DAYS - 1, W), dtype=np.int32)
+    bench.dump_outputs(str(tmp_path / 'b'), dict(history=longest, final_counters=final, first_day=1))
+    assert sum(p.stat().st_size for p in (tmp_path / 'b').iterdir()) <= 64_000_000
+    assert np.load(tmp_path / 'b' / 'history.npy').shape == longest.shape
