@@ -246,6 +246,9 @@ struct reina_engine {
     uint32_t walk_div = 16;                 // buckets of the ordered bed / ICU walk per walking workgroup of the install launch (REINA_WALK_DIV: measurement handle)
     uint32_t import_wgs = 16;               // most workgroups a day's imports are shared by (REINA_IMPORT_WGS: the tests' handle on the chunked paths)
     bool testing_ever = false;
+    uint32_t *d_snap = nullptr;             // snapshots (k_snapshot.inc): per-tile record counts, then their exclusive offsets, of both streams
+    uint32_t snap_total[2] = {0, 0};        // ... records of both streams as the last reina_snap_measure found them
+    uint32_t snap_qlen[3] = {0, 0, 0};      // ... and the lengths of queue0 / queue1 / level1
     bool fused_day = false;                 // stretches of days of a small unsharded population as ONE launch (k_small.inc; REINA_FUSED_DAY=1: measured SLOWER than the three launches a day, kept behind the switch with its tests)
     uint32_t small_wgs = 32;                // ... its workgroups (REINA_FUSED_WGS)
     uint32_t *d_bar = nullptr;              // ... its barrier counter, and the barriers passed so far

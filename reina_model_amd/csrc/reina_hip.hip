@@ -164,6 +164,7 @@ static void free_engine(reina_engine *e) {
     if (e->d_ref) (void)hipFree(e->d_ref);
     if (e->d_bar) (void)hipFree(e->d_bar);
     if (e->d_days) (void)hipFree(e->d_days);
+    if (e->d_snap) (void)hipFree(e->d_snap);
     for (size_t k = 0; k < e->days_stage.size(); k++) {
         (void)hipEventSynchronize(e->days_stage_ev[k]);
         (void)hipEventDestroy(e->days_stage_ev[k]);
@@ -1402,3 +1403,6 @@ int reina_profile_read(reina_engine_t *e, double *scan_ms_total, uint64_t *scan_
 }
 
 }  // extern "C"
+
+// snapshots of an engine between days (include/reina_snapshot.h): kernels and entry points
+#include "k_snapshot.inc"

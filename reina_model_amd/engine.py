@@ -342,6 +342,9 @@ class Engine:
     def __init__(self, lib, prefix, allocator, config, disease):
         self.f = bind_abi(lib, prefix)
         self.alloc = allocator
+        # snapshots (include/reina_snapshot.h): bound when the library has them, None otherwise
+        from .snapshot import bind_snapshot_abi
+        self.snap_f = bind_snapshot_abi(lib, prefix)
         self.config = config
         self._h = ctypes.c_void_p()
         self._check(self.f['create'](ctypes.byref(config), ctypes.byref(disease), ctypes.byref(self._h)), 'create')

@@ -23,13 +23,16 @@ import numpy as np
 from . import simulation
 
 
-def run_group_plan(contexts, plan, record_history=True, member_plans=None):
+def run_group_plan(contexts, plan, record_history=True, member_plans=None, group=None):
     """Execute `plan` (Context.make_plan) for all `contexts` as one engine group.  Returns
     history[len(contexts), days, COUNTER_WORDS] (host) or None.
 
     `member_plans` (one plan per context, see run_sweep): an intervention sweep -- the members' scenarios
     differ in the VALUES of their mobility limits / mask shares only, so they share the day descriptors
-    of `plan` while every member gets its own contact tables at each table change."""
+    of `plan` while every member gets its own contact tables at each table change.
+
+    `group`: an engine.EngineGroup of exactly these contexts' engines, made by the caller (run_branches restores its members
+    with one launch first); it stays open.  Otherwise a group is made for the run and closed after it."""
     from . import engine as _eng
     import os as _os, time as _time
     _T = [] if _os.environ.get('REINA_ENS_TIMING') else None   # (diagnostic: where a group run's wall time goes, tools/ens_first_run2.py)
@@ -37,7 +40,13 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None):
         if _T is not None:
             _T.append((name, _time.perf_counter()))
     _t('start')
-    group = _eng.EngineGroup([c.engine for c in contexts])
+    own_group = group is None
+    if own_group:
+        group = _eng.EngineGroup([c.engine for c in contexts])
+    elif [e._h.value for e in group.engines] != [c.engine._h.value for c in contexts]:
+        raise ValueError('run_group_plan: `group` is not the group of these contexts')
+    for c in contexts:
+        c._replayed = True
     a = group.alloc
     days = plan['days']
     K = len(contexts)
@@ -72,7 +81,8 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None):
         for c in contexts:
             c._raise_on_problem(c.engine.read_counters())
     _t('final counters')
-    group.close()
+    if own_group:
+        group.close()
     _t('closed')
     if _T is not None:
         print('run_group_plan: ' + ' | '.join('%s %.1f ms' % (n, (t - _T[k][1]) * 1e3) for k, (n, t) in enumerate(_T[1:])), flush=True)
@@ -178,3 +188,48 @@ def run_ensemble(variables, seeds, days, age_counts=None, device='cuda:0', threa
         with ThreadPoolExecutor(max_workers=min(threads, len(batch))) as pool:
             list(pool.map(work, batch))
     return np.stack(out)
+
+
+def run_branches(snap, variables, seeds, days, member_variables=None, age_counts=None, device='cuda:0', engine_factory=None,
+                 interventions=None):
+    """Conditional ensemble: K = len(seeds) futures of ONE realised past.  Every member is a Context of `variables` (or of
+    member_variables[m]) restored from `snap` (snapshot.Snapshot) -- on the device all K by one launch
+    (reina_group_snap_unpack) -- with its own seed, then `days` days are run as one engine group (run_group_plan).
+    member_variables follows run_sweep's rule: the members may differ only in the values of their mobility and mask
+    interventions.  `interventions`: intervention tuples of every member instead of its variables' scenario (make_context).
+    Returns (history[K, days, COUNTER_WORDS], contexts)."""
+    from . import engine as _eng
+    from . import snapshot as _snap
+    vs = list(member_variables) if member_variables is not None else [variables] * len(seeds)
+    if len(vs) != len(seeds):
+        raise ValueError('run_branches: one member_variables entry per seed')
+    plans = []
+    for v, sd in zip(vs, seeds):
+        if plans and v is vs[0]:
+            plans.append(plans[0])
+            continue
+        planner = simulation.make_context(v, age_counts=age_counts, seed=sd, device=device, engine_factory=engine_factory,
+                                          interventions=interventions)
+        planner.restore(snap, engine_state=False)
+        plans.append(planner.make_plan(days))
+        del planner
+    for k, p in enumerate(plans[1:], 1):
+        if p is not plans[0] and not _same_day_descriptors(plans[0], p):
+            raise ValueError('branch %d differs from branch 0 in more than the values of its mobility / mask '
+                             'interventions: it cannot share a group' % k)
+    ctxs = []
+    for v, sd in zip(vs, seeds):
+        c = simulation.make_context(v, age_counts=age_counts, seed=sd, device=device, engine_factory=engine_factory,
+                                   interventions=interventions)
+        c.restore(snap, engine_state=False)   # (host state and checks; the engines all at once below)
+        ctxs.append(c)
+    group = _eng.EngineGroup([c.engine for c in ctxs])
+    try:
+        _snap.unpack_group(group, ctxs[0]._disease, snap.image)
+        for c in ctxs:
+            c.engine.upload_contact_tables(*c._packed_tables_for_restore(snap.state))
+        member_plans = plans if member_variables is not None else None
+        hist = run_group_plan(ctxs, plans[0], member_plans=member_plans, group=group)
+    finally:
+        group.close()
+    return hist, ctxs

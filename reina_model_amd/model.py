@@ -374,6 +374,11 @@ class Context:
         self._keep = []
         self._iv_index = None
         self._iv_version = 0
+        # what restore() must know: a day has been built (iterate / run / make_plan), this Context made a plan (its host
+        # state ran ahead of its device state), its engine was replayed from a plan (the scenario state lives in the planner)
+        self._stepped = False
+        self._planner = False
+        self._replayed = False
         # sharded with a communicator of our own: the engine queues the pressure all-reduce itself
         self._in_stream = self._direct is not None and (self.n_shards > 1 or self.always_collective)
         if self._in_stream:
@@ -424,6 +429,7 @@ class Context:
         nrc, count, thr, meta, ranges = pack_contact_tables(t, self.nr_ages)
         mask = np.zeros((_eng.MAX_AGES, 8), dtype=np.float32)
         mask[:self.nr_ages, :6] = self.contact_matrix.mask_probabilities.astype(np.float32)
+        self._uploaded_mask = mask   # (mask shares take effect when tables are uploaded: what a snapshot carries)
         return nrc, count, thr, meta, mask, ranges
 
     def _upload_tables(self):
@@ -523,6 +529,7 @@ class Context:
         # (this function is host time per day, and a short run is host-bound -- DESIGN section 5: the interventions are indexed
         # by day number, a population that is not sharded splits nothing, and without a weekly import flow its float32
         # leftovers stay what they are: below 1, so no import either)
+        self._stepped = True
         ivs = self.interventions
         stamp = (len(ivs), self._iv_version, id(ivs[0]) if ivs else 0, id(ivs[-1]) if ivs else 0)
         if self._iv_index is None or self._iv_index[0] != stamp:
@@ -621,6 +628,7 @@ class Context:
         (reina_model_amd/ensemble.py).  Advances this Context's host-side state by `days`."""
         segments = []   # (packed tables or None, ctypes Day array, n)
         start_day = self.day
+        self._planner = True
         pending = []
         tables = None
         mobility = []
@@ -645,6 +653,7 @@ class Context:
         continue a replayed simulation with further plans of that same planner."""
         days = plan['days']
         a = self.engine.alloc
+        self._replayed = True
         hist = self._history_buffer(days) if record_history else None
         base = a.ptr(hist) if record_history else None
         done = 0
@@ -818,6 +827,107 @@ class Context:
         counters = self._read_counters_global()
         self._raise_on_problem(counters)
         return self.state_from_counters(counters)
+
+    # ------------------------------------------------------------------ snapshots (reina_model_amd/snapshot.py)
+    def _intervention_digest(self, before_day):
+        """(type, date, parameter values) of the interventions dated before `before_day`, in list order, as JSON values"""
+        import json
+        d0 = date.fromisoformat(self.start_date)
+        out = [iv.make_iv_tuple() for iv in self.interventions if (self._iv_date(iv) - d0).days < before_day]
+        return json.loads(json.dumps(out, default=lambda x: x.item() if hasattr(x, 'item') else str(x)))
+
+    def _check_snapshot_capable(self, what):
+        if self.n_shards != 1 or self.always_collective:
+            raise ValueError('%s: snapshots are taken of, and restored into, unsharded Contexts only' % what)
+        if self._planner:
+            raise ValueError('%s: this Context made a plan (make_plan): its host state ran ahead of its engine' % what)
+        if self._replayed:
+            raise ValueError('%s: this Context was replayed from a plan (run_plan / run_group_plan): its scenario state '
+                             'lives in the planner' % what)
+
+    def snapshot(self):
+        """The simulation as it stands between two days: a snapshot.Snapshot that Context.restore() continues from."""
+        from . import snapshot as _snap
+        self._check_snapshot_capable('snapshot')
+        counters = self._read_counters_global()
+        if int(counters[_eng.C_NR * _eng.MAX_AGES + _eng.S_PROBLEM]) != 0:
+            raise ValueError('snapshot: the simulation has failed (%s)' % PROBLEM_TO_STR.get(
+                int(counters[_eng.C_NR * _eng.MAX_AGES + _eng.S_PROBLEM]), 'problem'))
+        image = _snap.pack_engine(self.engine, self._disease, testing_ever=self.testing_mode != NO_TESTING)
+        cm = self.contact_matrix
+        f32 = lambda x: float(np.float32(x))
+        state = dict(
+            format=_snap.HOST_STATE_FORMAT, day=int(self.day), seed=int(self._seed), start_date=str(self.start_date),
+            n_agents=int(self.total_people), nr_ages=int(self.nr_ages), nr_variants=int(self.nr_variants),
+            testing_mode=int(self.testing_mode), p_detected_anyway=f32(self.p_detected_anyway),
+            p_successful_tracing=f32(self.p_successful_tracing),
+            vaccinations=[dict(min_age=v['min_age'], max_age=v['max_age'], slot=int(v['slot']), nr_daily=float(v.get('nr_daily', 0)))
+                          for v in self.vaccinations],
+            weekly_infections_amount=int(self.weekly_infections_amount),
+            weekly_infections_leftover=[float(x) for x in self.weekly_infections_leftover],
+            weekly_infections_shares=[float(x) for x in self.weekly_infections_shares],
+            pending_imports=[list(map(int, b)) for b in self._pending_imports], pending_beds=int(self._pending_beds),
+            pending_icu=int(self._pending_icu), sample_calls=int(self._sample_calls),
+            beds=int(self.beds), icu_units=int(self.icu_units),
+            mobility_factors=[[int(p), int(lo), int(hi), f32(fac)] for p, lo, hi, fac in cm.mobility_factors],
+            mobility_factor=f32(cm.mobility_factor), mask_probabilities=np.asarray(cm.mask_probabilities, dtype=np.float64).tolist(),
+            uploaded_mask=np.asarray(self._uploaded_mask, dtype=np.float32).astype(np.float64).tolist(),
+            interventions=self._intervention_digest(self.day))
+        return _snap.Snapshot(image, state)
+
+    def restore(self, snap, engine_state=True):
+        """Continue from `snap` (Context.snapshot) in this freshly made Context: same population, variants, disease and start
+        date; the seed may differ.  This Context keeps its own interventions and applies those dated on or after the
+        snapshot's day; those dated before it must be the ones the snapshot's run applied (ValueError otherwise).
+        `engine_state=False` restores the host state only (a planner of a restored ensemble, ensemble.run_branches)."""
+        from . import snapshot as _snap
+        st = snap.state
+        self._check_snapshot_capable('restore')
+        if self.day != 0 or self._stepped:
+            raise ValueError('restore: only into a freshly made Context (this one has stepped)')
+        if st.get('format') != _snap.HOST_STATE_FORMAT:
+            raise ValueError('restore: unknown host-state format %r' % st.get('format'))
+        if (st['n_agents'], st['nr_ages'], st['nr_variants']) != (self.total_people, self.nr_ages, self.nr_variants):
+            raise ValueError('restore: snapshot of another population or another number of variants')
+        if st['start_date'] != str(self.start_date):
+            raise ValueError('restore: snapshot starts on %s, this Context on %s' % (st['start_date'], self.start_date))
+        if self._intervention_digest(st['day']) != st['interventions']:
+            raise ValueError('restore: the interventions dated before day %d differ from those the snapshot ran with' % st['day'])
+        _snap.check_compatible(self.engine.config, self._disease, snap.header)
+        if engine_state:
+            _snap.unpack_engine(self.engine, self._disease, snap.image)
+        self._restore_host_state(st)
+        if engine_state:
+            self.engine.upload_contact_tables(*self._packed_tables_for_restore(st))
+        return self
+
+    def _restore_host_state(self, st):
+        self.day = int(st['day'])
+        self.testing_mode = int(st['testing_mode'])
+        self.p_detected_anyway = np.float32(st['p_detected_anyway'])
+        self.p_successful_tracing = np.float32(st['p_successful_tracing'])
+        self.vaccinations = [dict(v) for v in st['vaccinations']]
+        self.weekly_infections_amount = int(st['weekly_infections_amount'])
+        self.weekly_infections_leftover = [float(x) for x in st['weekly_infections_leftover']]
+        self.weekly_infections_shares = [float(x) for x in st['weekly_infections_shares']]
+        self._pending_imports = [tuple(b) for b in st['pending_imports']]
+        self._pending_beds, self._pending_icu = int(st['pending_beds']), int(st['pending_icu'])
+        self._sample_calls = int(st['sample_calls'])
+        self.beds, self.icu_units = int(st['beds']), int(st['icu_units'])
+        cm = self.contact_matrix
+        cm.mobility_factors = [[int(p), int(lo), int(hi), np.float32(f)] for p, lo, hi, f in st['mobility_factors']]
+        cm.mobility_factor = np.float32(st['mobility_factor'])
+        cm.mask_probabilities = np.asarray(st['mask_probabilities'], dtype=np.float64).reshape(self.nr_ages, len(PLACES))
+        cm.generate_contact_probabilities()   # (the tables of the snapshot's day: rebuilt on every mobility change)
+        cm.mobility_factor_changed = False
+
+    def _packed_tables_for_restore(self, st):
+        """the contact tables as the snapshot's engine last had them: built from the mobility state, with the mask shares
+        of their last upload (a mask change takes effect at the next table upload)"""
+        nrc, count, thr, meta, mask, ranges = self._packed_tables()
+        mask = np.asarray(st['uploaded_mask'], dtype=np.float32).reshape(mask.shape)
+        self._uploaded_mask = mask
+        return nrc, count, thr, meta, mask, ranges
 
     # main.pyx:2047-2101
     SAMPLE_KINDS = ('contacts_per_day', 'symptom_severity', 'incubation_period', 'illness_period',

@@ -53,10 +53,14 @@ def create_disease_params(variables):
 
 
 def make_context(variables, age_counts=None, seed=None, interventions=None, device='cuda:0',
-                 engine_factory=None, comm=None, ipc=None, strict=False):
+                 engine_factory=None, comm=None, ipc=None, strict=False, snapshot=None):
     """Build a Context the way calc/simulation.py:148-180 does.  `ipc`: an InitialPopulationCondition,
     a dict of its fields, None (no initial condition), or 'auto' = what simulate_individuals passes,
-    datasets.get_initial_population_condition(variables) (calc/simulation.py:152)."""
+    datasets.get_initial_population_condition(variables) (calc/simulation.py:152).
+    `snapshot` (snapshot.Snapshot): the Context continues from it (Context.restore); no initial condition is applied, the
+    state is replaced."""
+    if snapshot is not None:
+        ipc = None
     if isinstance(ipc, str) and ipc == 'auto':
         ipc = datasets.get_initial_population_condition(variables)
     if age_counts is None:
@@ -81,6 +85,8 @@ def make_context(variables, age_counts=None, seed=None, interventions=None, devi
         ivs = [iv_tuple_to_obj(iv, vnames) for iv in interventions]
     for iv in ivs:
         ctx.add_intervention(iv)
+    if snapshot is not None:
+        ctx.restore(snapshot)
     return ctx
 
 
@@ -137,6 +143,53 @@ def simulate_individuals(variables=None, step_callback=None, callback_day_interv
     adf = adf.unstack('attr').unstack('age_group')
     adf.columns = adf.columns.droplevel()
     return df, adf
+
+
+def simulate_with_snapshots(variables=None, snapshot_days=(), days=None, device='cuda:0', engine_factory=None, age_counts=None):
+    """simulate_individuals' run that also takes a snapshot (snapshot.Snapshot) before each of `snapshot_days` (0 <= d <=
+    days).  Returns (df, adf, {day: Snapshot}); each snapshot carries the history rows and mobility history of the days
+    before it, so resume_individuals can give the frames of the whole horizon."""
+    if variables is None:
+        variables = copy_variables()
+    ctx = make_context(variables, age_counts=age_counts, device=device, engine_factory=engine_factory,
+                       ipc=datasets.get_initial_population_condition(variables))
+    days = variables['simulation_days'] if days is None else int(days)
+    wanted = sorted(set(int(d) for d in snapshot_days))
+    if wanted and (wanted[0] < 0 or wanted[-1] > days):
+        raise ValueError('snapshot days must lie in [0, %d]' % days)
+    t0 = time.perf_counter()
+    hists, mobility, snaps, done = [], [], {}, 0
+    for d in wanted + [days]:
+        if d > done:
+            hists.append(ctx.run(d - done))
+            mobility += ctx.mobility_history
+            done = d
+        if d in wanted:
+            h = np.concatenate(hists) if hists else np.zeros((0, _eng.COUNTER_WORDS), dtype=np.int32)
+            snaps[d] = ctx.snapshot().with_history(h, list(mobility))
+    hist = np.concatenate(hists) if hists else np.zeros((0, _eng.COUNTER_WORDS), dtype=np.int32)
+    df, adf = _frames_from_history(ctx, hist, mobility, date.fromisoformat(variables['start_date']),
+                                   (time.perf_counter() - t0) * 1000 / max(days, 1))
+    return df, adf, snaps
+
+
+def resume_individuals(snap, variables=None, seed=None, device='cuda:0', engine_factory=None, age_counts=None):
+    """simulate_individuals' frames for the whole horizon of `variables`, the days before `snap` from its history and the rest
+    run from it -- with `variables`' own interventions from the snapshot's day on (a what-if of the future), and `seed` (default:
+    the snapshot's) for the days to come."""
+    if variables is None:
+        variables = copy_variables()
+    if snap.history is None:
+        raise ValueError('resume_individuals: the snapshot carries no history (take it with simulate_with_snapshots)')
+    ctx = make_context(variables, age_counts=age_counts, seed=snap.seed if seed is None else seed, device=device,
+                       engine_factory=engine_factory, snapshot=snap)
+    days = variables['simulation_days']
+    t0 = time.perf_counter()
+    rest = ctx.run(days - snap.day) if days > snap.day else np.zeros((0, _eng.COUNTER_WORDS), dtype=np.int32)
+    ms = (time.perf_counter() - t0) * 1000 / max(days - snap.day, 1)
+    hist = np.concatenate([snap.history, rest])
+    mobility = list(snap.mobility_history) + list(ctx.mobility_history if days > snap.day else [])
+    return _frames_from_history(ctx, hist, mobility, date.fromisoformat(variables['start_date']), ms)
 
 
 def _frames_from_history(ctx, hist, mobility_history, start_date, ms_per_day=0.0, want_adf=True):
