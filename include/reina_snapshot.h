@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define REINA_SNAPSHOT_VERSION 1
+#define REINA_SNAPSHOT_VERSION 2   /* 2: the FNV-1a 64 hashes of the header with the standard offset basis (1 had a wrong one) */
 #define REINA_SNAP_MAGIC 0x504E5352u   /* "RSNP" */
 #define REINA_SNAP_TILE 512u           /* agents per tile of the offset tables (k_day's wave tiles) */
 #define REINA_SNAP_HEADER_WORDS 64u

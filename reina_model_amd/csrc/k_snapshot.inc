@@ -268,7 +268,7 @@ __global__ __launch_bounds__(SNAP_UNPACK_THREADS) void k_snap_unpack(const Membe
 
 static uint64_t snap_fnv1a(const void *p, size_t n) {
     const unsigned char *b = static_cast<const unsigned char *>(p);
-    uint64_t h = 1469598103934665603ull;
+    uint64_t h = 14695981039346656037ull;   // FNV-1a 64: offset basis 0xCBF29CE484222325, prime 2^40 + 2^8 + 0xB3
     for (size_t k = 0; k < n; k++) {
         h ^= b[k];
         h *= 1099511628211ull;

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import engine as _eng
 
-SNAPSHOT_VERSION = 1           # include/reina_snapshot.h: REINA_SNAPSHOT_VERSION
+SNAPSHOT_VERSION = 2           # include/reina_snapshot.h: REINA_SNAPSHOT_VERSION
 MAGIC = 0x504E5352             # "RSNP"
 TILE = 512
 HEADER_WORDS = 64
@@ -55,7 +55,7 @@ def bind_snapshot_abi(lib, prefix):
 
 
 def fnv1a64(data):
-    h = 1469598103934665603
+    h = 14695981039346656037   # (FNV-1a 64: offset basis 0xCBF29CE484222325, prime 2^40 + 2^8 + 0xB3)
     for b in bytes(data):
         h = ((h ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
     return h

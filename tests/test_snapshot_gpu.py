@@ -1,15 +1,18 @@
 """Snapshots on the MI355X (include/reina_snapshot.h: k_snap_count / k_snap_scan / k_snap_pack / k_snap_unpack): a restored
 GPU run is the uninterrupted one, the GPU packer writes the numpy packer's bytes, a snapshot continues with a NEW seed on the
-GPU exactly as on oracle B (both ways), an engine-group fork equals single restores, and a 5e7-agent state round-trips."""
+GPU exactly as on oracle B (both ways), ragged populations snapshot as on oracle B, an engine-group fork (large and small
+populations) equals single restores, and a 5e7-agent state packs to the format and round-trips."""
 import copy
 
 import numpy as np
 import pytest
 
 import par_backend
+import snap_util
 from golden_util import load_run, variables_for
 from reina_model_amd import datasets, ensemble, simulation, snapshot as snapmod
 from reina_model_amd import engine as eng
+from reina_model_amd.model import NO_TESTING
 from reina_model_amd.variables import VARIABLE_DEFAULTS
 
 pytestmark = pytest.mark.gpu
@@ -40,6 +43,33 @@ def _same_state(a, b):
         assert ca[l] == cb[l], q
         assert np.array_equal(np.sort(_host(a, q)[:ca[l]]), np.sort(_host(b, q)[:cb[l]])), q
     assert np.array_equal(list_pairs(a), list_pairs(b)), 'infectee lists'
+
+
+# words of the control block that carry state from one day to the next in both engines: the queue lengths and the
+# vaccination cursors (include/reina_hip.h REINA_L_*).  The others are the day's list lengths, tickets and diagnostics, which
+# each engine keeps its own way (the GPU's day-open word, active-agent counts and hospital peak; oracle B's list lengths)
+# and resets before it reads them (test_cross_engine_continuation_with_a_new_seed).
+CARRIED_CONTROL = [2, 3, 4] + list(range(32, 48))
+
+
+def _assert_image_equals_oracle_bs(wg, wc):
+    """a GPU image against oracle B's of the same state: every word but the control block's per-day words; the queues
+    as multisets (the GPU appends to them with atomics, in no fixed order; _same_state compares them so too)"""
+    assert len(wg) == len(wc)
+    g, c = wg.view(np.uint32), wc.view(np.uint32)
+    h = snapmod.parse_header(c)
+    lay = snapmod.layout(h['n_agents'], h['n_base'], h['n_slot'], h['qlen'])
+    at = snapmod.HEADER_WORDS + eng.COUNTER_WORDS
+    same = np.ones(lay['q'], dtype=bool)
+    same[at:at + eng.L_NR] = False
+    same[at + np.array(CARRIED_CONTROL)] = True
+    bad = np.flatnonzero((g[:lay['q']] != c[:lay['q']]) & same)
+    assert len(bad) == 0, 'words %s differ: %s != %s' % (bad[:8], g[bad[:8]], c[bad[:8]])
+    q = lay['q']
+    for k, n in enumerate(h['qlen']):
+        assert np.array_equal(np.sort(g[q:q + n]), np.sort(c[q:q + n])), 'queue %d' % k
+        q += n
+    assert q == len(c)
 
 
 def _kitchen():
@@ -87,14 +117,57 @@ def test_gpu_packer_writes_the_numpy_packers_bytes():
     g, c = _gpu(v, ages, seed, ivs), _cpu(v, ages, seed, ivs)
     assert np.array_equal(g.run(80), c.run(80))
     sg, sc = g.snapshot().to_host(), c.snapshot()
-    wg, wc = sg.image.view(np.uint32), sc.image.view(np.uint32)
     assert sg.header['n_base'] == sc.header['n_base'] and sg.header['n_slot'] == sc.header['n_slot']
     assert sg.header['n_slot'] > 0 and sg.header['testing_ever'] == sc.header['testing_ever']
-    lay = snapmod.layout(g.total_people, sg.header['n_base'], sg.header['n_slot'], sg.header['qlen'])
-    assert np.array_equal(wg[lay['tb']:lay['q']], wc[lay['tb']:lay['q']]), 'tile tables and record streams'
-    assert np.array_equal(wg[:snapmod.HEADER_WORDS], wc[:snapmod.HEADER_WORDS]), 'header'
-    assert np.array_equal(wg[snapmod.HEADER_WORDS:snapmod.HEADER_WORDS + eng.COUNTER_WORDS],
-                          wc[snapmod.HEADER_WORDS:snapmod.HEADER_WORDS + eng.COUNTER_WORDS]), 'counters'
+    # the whole image: header, counters, the carried control words, tile tables, pad, record streams, queues
+    _assert_image_equals_oracle_bs(sg.image, sc.image)
+
+
+@pytest.mark.parametrize('total', [4099, 10007])
+def test_ragged_population_snapshot_is_oracle_bs_and_continues(total):
+    """test_parity_gpu's ragged populations (N not a multiple of the tile, nor of the wave): on day 60 the GPU image is oracle
+    B's byte for byte but for the control block's per-day words, and a GPU restore runs to day 120 as the uninterrupted run"""
+    v = copy.deepcopy(VARIABLE_DEFAULTS)
+    v.update(hospital_beds=3, icu_units=1)
+    ages = datasets.scaled_population(total)
+    g, c = _gpu(v, ages, 11), _cpu(v, ages, 11)
+    assert np.array_equal(g.run(60), c.run(60))
+    sg, sc = g.snapshot(), c.snapshot()
+    wg, wc = sg.to_host().image, sc.image
+    assert sc.header['n_base'] > 0 and total % snapmod.TILE != 0
+    _assert_image_equals_oracle_bs(wg, wc)
+    b = _gpu(v, ages, 11, snap=sg)
+    assert np.array_equal(b.run(60), g.run(60))
+    _same_state(g, b)
+
+
+def test_small_population_fork_equals_single_restores():
+    """the kitchen-sink run forked on day 70 into 40 seeds (T = 59 tiles: the group unpack splits the members over several
+    chunks of blockIdx.y, the last one ragged on a 256-CU chip); every member is the single restore with its seed"""
+    import torch
+    v, ages, seed, ivs = _kitchen()
+    v = dict(v, simulation_days=200)
+    a = _gpu(v, ages, seed, ivs)
+    a.run(70)
+    snap = a.snapshot()
+    seeds = [seed] + [300 + k for k in range(39)]
+    chunks, per, last = snap_util.group_geometry(snap.header['n_tiles'], len(seeds),
+                                                 torch.cuda.get_device_properties(0).multi_processor_count)
+    assert chunks > 1, (chunks, per, last)
+    hist, members = ensemble.run_branches(snap, v, seeds, 30, age_counts=ages, interventions=ivs)
+    assert hist.shape == (40, 30, eng.COUNTER_WORDS)
+    assert np.array_equal(hist[0], a.run(30))
+    for m, sd in enumerate(seeds):
+        one = _gpu(v, ages, sd, ivs, snap=snap)
+        assert np.array_equal(one.run(30), hist[m]), m
+        _same_state(one, members[m])
+        del one
+    host = snap.to_host()
+    for m in (1, 39):
+        b = _cpu(v, ages, seeds[m], ivs, snap=host)
+        assert np.array_equal(b.run(30), hist[m]), m
+        _same_state(members[m], b)
+    assert not np.array_equal(hist[1], hist[39])
 
 
 def test_cross_engine_continuation_with_a_new_seed(tmp_path):
@@ -142,6 +215,14 @@ def test_group_fork_equals_single_restores():
     assert not np.array_equal(hist[1], hist[2])
 
 
+class _HostCopy:
+    """host copies of a HIP engine's persistent arrays, in the shape pack_numpy reads"""
+
+    def __init__(self, ctx):
+        self.config = ctx.engine.config
+        self.tensors = {k: _host(ctx, k) for k in ('hot', 'cold', 'infectees', 'counters', 'control', 'queue0', 'queue1', 'level1')}
+
+
 def test_scale_5e7_agents_pack_unpack_continue():
     v = copy.deepcopy(VARIABLE_DEFAULTS)
     ages = datasets.scaled_population(50_000_000)
@@ -150,9 +231,15 @@ def test_scale_5e7_agents_pack_unpack_continue():
     snap = a.snapshot()
     dense = 4 * a.total_people * (1 + eng.COLD_WORDS + eng.INLINE_INFECTEES)
     assert snap.nbytes < dense
+    # the GPU image is the format of the engine's arrays (pack_numpy over host copies of them, 3.5 GB)
+    want = snapmod.pack_numpy(_HostCopy(a), a._disease, a.testing_mode != NO_TESTING)
+    got = snap.image.cpu().numpy()
+    assert len(got) == len(want) and np.array_equal(got, want), np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))[:8]
+    del want, got
     b = _gpu(v, ages, 2, snap=snap)
     del snap
     ha, hb = a.run(10), b.run(10)
     assert np.array_equal(ha, hb)
     assert np.array_equal(a.engine.read_counters(), b.engine.read_counters())
     assert np.array_equal(_host(a, 'hot'), _host(b, 'hot'))
+    _same_state(a, b)
