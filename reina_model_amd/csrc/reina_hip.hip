@@ -1406,3 +1406,6 @@ int reina_profile_read(reina_engine_t *e, double *scan_ms_total, uint64_t *scan_
 
 // snapshots of an engine between days (include/reina_snapshot.h): kernels and entry points
 #include "k_snapshot.inc"
+
+// transmission-tree reports of an engine between days (include/reina_transmission.h): kernels and entry points
+#include "k_transmission.inc"

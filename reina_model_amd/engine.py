@@ -345,6 +345,9 @@ class Engine:
         # snapshots (include/reina_snapshot.h): bound when the library has them, None otherwise
         from .snapshot import bind_snapshot_abi
         self.snap_f = bind_snapshot_abi(lib, prefix)
+        # transmission-tree reports (include/reina_transmission.h): likewise
+        from .transmission import bind_tx_abi
+        self.tx_f = bind_tx_abi(lib, prefix)
         self.config = config
         self._h = ctypes.c_void_p()
         self._check(self.f['create'](ctypes.byref(config), ctypes.byref(disease), ctypes.byref(self._h)), 'create')

@@ -233,3 +233,30 @@ def run_branches(snap, variables, seeds, days, member_variables=None, age_counts
     finally:
         group.close()
     return hist, ctxs
+
+
+def transmission_reports(contexts, age_groups=None, group=None):
+    """Context.transmission_report of every context, between the same two days: the members' reports as ONE launch per pass on
+    the device (reina_group_tx_report), one report per member for host-memory engines.  `group`: an engine.EngineGroup of
+    exactly these contexts' engines (stays open); otherwise one is made for the call and closed after it."""
+    from . import engine as _eng, transmission as _tx
+    contexts = list(contexts)
+    for c in contexts:
+        c._check_tx_capable()
+    table, labels = contexts[0]._tx_groups(age_groups)
+    if getattr(contexts[0].engine.alloc, 'torch', None) is None:
+        reps = [_tx.report_engine(c.engine, table, len(labels)) for c in contexts]
+    else:
+        own_group = group is None
+        if own_group:
+            group = _eng.EngineGroup([c.engine for c in contexts])
+        elif [e._h.value for e in group.engines] != [c.engine._h.value for c in contexts]:
+            raise ValueError('transmission_reports: `group` is not the group of these contexts')
+        try:
+            reps = _tx.report_group(group, table, len(labels))
+        finally:
+            if own_group:
+                group.close()
+    for r in reps:
+        r.group_labels = labels
+    return reps

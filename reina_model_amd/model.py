@@ -875,6 +875,35 @@ class Context:
             interventions=self._intervention_digest(self.day))
         return _snap.Snapshot(image, state)
 
+    # ------------------------------------------------------------------ transmission reports (reina_model_amd/transmission.py)
+    def _tx_groups(self, age_groups):
+        """(per-age group table, labels) of Context.transmission_report's `age_groups`"""
+        if age_groups is None:
+            return self.age_group_indices[:self.nr_ages], list(self.age_group_labels)
+        if isinstance(age_groups, dict):
+            return np.asarray(age_groups['age_indices'])[:self.nr_ages], list(age_groups['labels'])
+        g = np.asarray(age_groups, dtype=np.int64)[:self.nr_ages]
+        return g, [str(k) for k in range(int(g.max()) + 1 if len(g) else 1)]
+
+    def _check_tx_capable(self):
+        if self.n_shards != 1 or self.always_collective:
+            raise ValueError('transmission_report: reports are taken of unsharded Contexts only')
+        counters = self._read_counters_global()
+        problem = int(counters[_eng.C_NR * _eng.MAX_AGES + _eng.S_PROBLEM])
+        if problem != 0:
+            raise ValueError('transmission_report: the simulation has failed (%s)' % PROBLEM_TO_STR.get(problem, 'problem'))
+
+    def transmission_report(self, age_groups=None):
+        """Who infected whom, between two days: a transmission.TransmissionReport (offspring distribution, age matrix,
+        generations, clusters).  age_groups: None = the Context's report groups, a per-age sequence of group indices
+        (< 16), or a dict(labels=..., age_indices=...).  Reads the engine's state only: the simulation continues unchanged."""
+        from . import transmission as _tx
+        self._check_tx_capable()
+        table, labels = self._tx_groups(age_groups)
+        r = _tx.report_engine(self.engine, table, len(labels))
+        r.group_labels = labels
+        return r
+
     def restore(self, snap, engine_state=True):
         """Continue from `snap` (Context.snapshot) in this freshly made Context: same population, variants, disease and start
         date; the seed may differ.  This Context keeps its own interventions and applies those dated on or after the

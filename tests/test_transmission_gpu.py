@@ -1,0 +1,154 @@
+"""Transmission-tree reports on the GPU: the library's kernels (reina_tx_report, reina_group_tx_report) against the numpy
+specification on synthetic forests and on real runs, and against oracle B report for report."""
+import copy
+
+import numpy as np
+import pytest
+
+import par_backend
+import snap_util
+import tx_util
+from golden_util import load_run, variables_for
+from reina_model_amd import datasets, ensemble, simulation, transmission as tx
+from reina_model_amd import engine as eng
+from reina_model_amd.variables import VARIABLE_DEFAULTS
+
+pytestmark = pytest.mark.gpu
+
+
+def _spec_like_engine(hot, inf, cnt, age_start, groups, day, n):
+    """report_numpy with report_engine's depths: the day word + 1 first, every chain when that leaves agents unconverged"""
+    r = tx.report_numpy(hot, inf, cnt, age_start, groups, min(max(day, 0), eng.MAX_DAYS) + 1)
+    return tx.report_numpy(hot, inf, cnt, age_start, groups, n) if r.unconverged else r
+
+
+def _assert_same(got, want):
+    bad = np.flatnonzero(got.words != want.words)
+    assert not len(bad), [(int(k), int(got.words[k]), int(want.words[k])) for k in bad[:8]]
+
+
+def _forest_case(n, pattern, size=None, day=4095, kind='default'):
+    hot, inf, cnt = tx_util.forest(n, pattern, size=size)
+    ctx = snap_util.make_context(n)
+    tx_util.put_forest(ctx, hot, inf, cnt, day=day)
+    g = tx_util.groups(kind)
+    got = tx.report_engine(ctx.engine, g)
+    want = _spec_like_engine(hot, inf, cnt, np.asarray(ctx.engine.config.age_start), g, day, n)
+    _assert_same(got, want)
+    return got
+
+
+@pytest.mark.parametrize('n', (1, 511, 512, 513, 3 * 512 + 7))
+@pytest.mark.parametrize('pattern', tx_util.PATTERNS)
+def test_kernels_equal_spec_on_forests(pattern, n):
+    _forest_case(n, pattern, kind='fine' if n % 2 else 'default')
+
+
+def test_kernels_equal_spec_on_large_forests():
+    n = 3_000_000
+    r = _forest_case(n, 'random')
+    assert r.n_roots > 0 and r.unconverged == 0
+    r = _forest_case(n, 'bad_links')
+    assert r.bad_links > 0
+    r = _forest_case(n, 'giant', size=2_000_000)          # one cluster of 2e6 agents: the tally's aggregation
+    assert r.largest_cluster == 2_000_000 and r.n_roots == 1
+    r = _forest_case(n, 'star', size=1_000_000)           # a star of 1e6: one agent in bin 63
+    assert r.offspring[..., 63].sum() == 1 and r.sum_n_infected == 999_999
+    r = _forest_case(n, 'roots')
+    assert r.clusters[0] == n and r.largest_root == 0
+
+
+def test_deep_chain_takes_the_second_pass():
+    # a chain of 5000 in an engine whose day word says 3 days have run: the first pass resolves 3 links, the second all
+    r = _forest_case(6000, 'chain', size=5000, day=3)
+    assert r.rounds == tx.rounds_for(6000) and r.unconverged == 0 and r.max_generation == 4999
+    r = _forest_case(3_000_000, 'chain', size=5000, day=3)
+    assert r.rounds == tx.rounds_for(3_000_000) and r.max_generation == 4999
+
+
+def _pair(v, ages, seed, days, ivs=None):
+    g = simulation.make_context(v, age_counts=ages, seed=seed, interventions=ivs)
+    c = simulation.make_context(v, age_counts=ages, seed=seed, interventions=ivs, engine_factory=par_backend.par_engine_factory)
+    assert np.array_equal(g.run(days), c.run(days))
+    return g, c
+
+
+def test_gpu_report_equals_oracle_b_report():
+    g, c = _pair(snap_util.variables(), snap_util.population(20000), 1, 150)
+    rg, rc = g.transmission_report(), c.transmission_report()
+    _assert_same(rg, rc)
+    assert rg.n_linked > 1000 and rg.unconverged == 0
+    _, meta = load_run('mini_kitchen_s0')
+    g, c = _pair(variables_for(meta), np.asarray(meta['age_counts']), meta['seed'], 120, meta['interventions'])
+    _assert_same(g.transmission_report(), c.transmission_report())
+
+
+def _host_state(ctx):
+    n = ctx.engine.config.n_agents
+    t = ctx.engine.tensors
+    hot = t['hot'].cpu().numpy().view(np.uint32)
+    rec = t['cold'].view(n, eng.COLD_WORDS)[:, 2:4].cpu().numpy()
+    return hot, rec[:, 0].copy(), rec[:, 1].copy(), int(t['counters'][eng.C_NR * eng.MAX_AGES + eng.S_DAY])
+
+
+def test_hus_day_200_invariants():
+    v = copy.deepcopy(VARIABLE_DEFAULTS)
+    ctx = simulation.make_context(v, age_counts=datasets.get_population_for_area('HUS'), seed=5)
+    hist = ctx.run(200)
+    r = ctx.transmission_report()
+    assert r.n_linked == r.sum_n_infected == int(r.matrix.sum())
+    assert int(r.generations.sum()) == int(r.cluster_agents.sum()) == r.n_infected_agents
+    assert r.bad_links == r.unconverged == 0 and r.rounds == tx.rounds_for(201)
+    base = eng.C_NR * eng.MAX_AGES
+    final = ctx.engine.read_counters()
+    assert int(r.offspring[:, :, 1].sum()) == int(hist[1:, base + eng.S_TOTAL_INFECTORS].sum()) + int(final[base + eng.S_TOTAL_INFECTORS])
+    assert int(r.offspring_sum[:, 1].sum()) == int(hist[1:, base + eng.S_TOTAL_INFECTIONS].sum()) + int(final[base + eng.S_TOTAL_INFECTIONS])
+    hot, inf, cnt, day = _host_state(ctx)
+    _assert_same(r, _spec_like_engine(hot, inf, cnt, np.asarray(ctx.engine.config.age_start), ctx.age_group_indices[:ctx.nr_ages], day, len(hot)))
+
+
+def test_group_report_equals_single_reports():
+    v = snap_util.variables()
+    ages = datasets.scaled_population(50000)
+    ctxs = [simulation.make_context(v, age_counts=ages, seed=s) for s in range(16)]
+    plan = ctxs[0].make_plan(90)
+    ensemble.run_group_plan(ctxs, plan)
+    reps = ensemble.transmission_reports(ctxs)
+    singles = [c.transmission_report() for c in ctxs]
+    for a, b in zip(reps, singles):
+        _assert_same(a, b)
+    assert len({r.n_infected_agents for r in reps}) > 1
+    # a member whose chains outrun its day word is reported again with every chain resolved (synthetic state, 2 members)
+    two = [simulation.make_context(v, age_counts=snap_util.population(4000), seed=s) for s in (1, 2)]
+    hot, inf, cnt = tx_util.forest(4000, 'chain', size=3000)
+    tx_util.put_forest(two[0], hot, inf, cnt, day=2)
+    hot2, inf2, cnt2 = tx_util.forest(4000, 'random')
+    tx_util.put_forest(two[1], hot2, inf2, cnt2, day=200)
+    reps = ensemble.transmission_reports(two)
+    _assert_same(reps[0], two[0].transmission_report())
+    _assert_same(reps[1], two[1].transmission_report())
+    assert reps[0].max_generation == 2999 and reps[0].unconverged == 0
+
+
+def test_report_between_days_does_not_change_the_gpu_continuation():
+    v = copy.deepcopy(VARIABLE_DEFAULTS)
+    ages = datasets.get_population_for_area('HUS')
+    a = simulation.make_context(v, age_counts=ages, seed=9)
+    b = simulation.make_context(v, age_counts=ages, seed=9)
+    ha = np.concatenate([a.run(60), (a.transmission_report(), a.run(60))[1]])
+    hb = b.run(120)
+    assert np.array_equal(ha, hb)
+    assert np.array_equal(a.engine.read_counters(), b.engine.read_counters())
+    for name in ('hot', 'cold'):
+        assert bool((a.engine.tensors[name] == b.engine.tensors[name]).all()), name
+
+
+def test_scale_5e7_report_equals_spec():
+    v = copy.deepcopy(VARIABLE_DEFAULTS)
+    ctx = simulation.make_context(v, age_counts=datasets.scaled_population(50_000_000), seed=2)
+    ctx.run(120, record_history=False)
+    r = ctx.transmission_report()
+    hot, inf, cnt, day = _host_state(ctx)
+    want = _spec_like_engine(hot, inf, cnt, np.asarray(ctx.engine.config.age_start), ctx.age_group_indices[:ctx.nr_ages], day, len(hot))
+    _assert_same(r, want)
+    assert r.n_infected_agents > 100_000 and r.unconverged == 0
