@@ -1409,3 +1409,6 @@ int reina_profile_read(reina_engine_t *e, double *scan_ms_total, uint64_t *scan_
 
 // transmission-tree reports of an engine between days (include/reina_transmission.h): kernels and entry points
 #include "k_transmission.inc"
+
+// the particle filter's in-group clone (include/reina_filter.h): kernel and entry point
+#include "k_filter.inc"

@@ -75,6 +75,21 @@ def make_age_groups(max_age=100):
     return out
 
 
+def get_detected_cases(area_name='HUS'):
+    """calc/datasets.py:93-103: the area's case rows as a DataFrame indexed by date (datetime.date) with the columns dead,
+    in_icu, in_ward, all_detected (the file's `confirmed`, renamed as the reference does).  `area_name` may also be a
+    variables dict (the reference's argument)."""
+    import pandas as pd
+    if isinstance(area_name, dict):
+        area_name = area_name['area_name']
+    d = _load(area_name)
+    cols = list(d['case_columns'])
+    df = pd.DataFrame([list(r) for r in d['case_rows']], columns=cols)
+    df['date'] = pd.to_datetime(df['date']).dt.date
+    df = df.set_index('date')
+    return df.drop(columns=[c for c in ('hospitalized',) if c in df.columns]).rename(columns=dict(confirmed='all_detected'))
+
+
 @dataclass
 class InitialPopulationCondition:
     """calc/datasets.py:106-134: how many people are in which state when the simulation starts."""

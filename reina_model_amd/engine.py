@@ -348,6 +348,9 @@ class Engine:
         # transmission-tree reports (include/reina_transmission.h): likewise
         from .transmission import bind_tx_abi
         self.tx_f = bind_tx_abi(lib, prefix)
+        # the particle filter's in-group clone (include/reina_filter.h): likewise
+        from .filtering import bind_filter_abi
+        self.filter_f = bind_filter_abi(lib, prefix)
         self.config = config
         self._h = ctypes.c_void_p()
         self._check(self.f['create'](ctypes.byref(config), ctypes.byref(disease), ctypes.byref(self._h)), 'create')

@@ -1,0 +1,500 @@
+"""Particle filters: condition a Monte-Carlo ensemble on observed case counts (include/reina_filter.h; DESIGN.md "Particle
+filter").
+
+A bootstrap particle filter (sequential Monte Carlo) over ONE engine group: K member Contexts of one scenario, differing
+only in their seed, run window by window from one planner's plans (Context.make_plan + ensemble.run_group_plan).  After
+each window the members' history rows are scored against the observations on the host (a negative-binomial observation
+model, float64), the weights are updated and, when the effective sample size falls below ess_threshold * K, the members
+are resampled systematically.  Resampling moves device state only: member dst is overwritten by member src's carried
+state (reina_group_clone: one launch for all pairs) and continues as an independent future under its own seed -- the RNG
+is Philox keyed by the seed, so nothing is reseeded, and under one plan the members' host state is the same.
+
+This module also holds clone_state, the numpy specification of the clone and the path for host-memory engines.
+
+Alignment: an observation dated t is scored against history row d = t - start_date, the state before day d (what the
+reference's frames show on that date).  Rows outside the filter's horizon are ignored.
+"""
+import ctypes
+import math
+import time
+from datetime import date, datetime
+
+import numpy as np
+
+from . import engine as _eng
+
+FILTER_VERSION = 1              # include/reina_filter.h: REINA_FILTER_VERSION
+CLONE_MAX_PAIRS = 896           # REINA_CLONE_MAX_PAIRS: pairs per launch
+FILTER_FUNCTIONS = ('filter_version', 'group_clone')
+TILE = 512
+# k_init's cold record: claim (2 words) ~0, infector -1, n_infected 0, onset 0.0, vacc_day -1, first_infectee -1, next_sibling -1
+COLD_DEFAULT = np.array([0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF, 0, 0, 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF], dtype=np.uint32)
+L_QUEUE0 = 2                    # REINA_L_QUEUE0 (queue1, level1 follow)
+# observed stream -> (counter, cumulative?): cumulative streams are compared as increments between observed dates
+STREAMS = {'all_detected': ('all_detected', True), 'dead': ('dead', True),
+           'in_ward': ('in_ward', False), 'in_icu': ('in_icu', False)}
+
+
+def bind_filter_abi(lib, prefix):
+    """The particle-filter entry points of a library, or None when it has none."""
+    if not all(hasattr(lib, prefix + n) for n in FILTER_FUNCTIONS):
+        return None
+    f = {n: getattr(lib, prefix + n) for n in FILTER_FUNCTIONS}
+    f['filter_version'].argtypes = []
+    f['group_clone'].argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+    for n in FILTER_FUNCTIONS:
+        f[n].restype = ctypes.c_int
+    if f['filter_version']() != FILTER_VERSION:
+        raise _eng.EngineError('%sfilter_version() = %d, this binding is written for %d' % (prefix, f['filter_version'](), FILTER_VERSION))
+    return f
+
+
+# ------------------------------------------------------------------------------------------------ the clone
+
+def clone_state(dst, src, n_agents, max_queue):
+    """The specification of reina_group_clone for one pair: dst (a dict of uint32 numpy arrays: hot [n], cold [n, 8],
+    infectees [n, 8], counters, control, queue0, queue1, level1, active_bits, infected_bits) gets src's carried state, in
+    place.  Agents recorded in src get src's hot word, cold record and slots; agents recorded only in dst get k_init's
+    words; agents susceptible in both are not touched.  The bit-plane words of the n_tiles tiles, the dense blocks, and the
+    queues up to src's lengths (clamped to [0, max_queue]) are copied."""
+    n = int(n_agents)
+    sh, dh = src['hot'][:n], dst['hot'][:n]
+    rec = sh != 0
+    clear = ~rec & (dh != 0)
+    dst['cold'][rec] = src['cold'][rec]
+    dst['infectees'][rec] = src['infectees'][rec]
+    dst['cold'][clear] = COLD_DEFAULT
+    dst['infectees'][clear] = 0xFFFFFFFF
+    dh[:] = sh
+    for name in ('counters', 'control'):
+        dst[name][:] = src[name]
+    for k, name in enumerate(('queue0', 'queue1', 'level1')):
+        ln = min(max(int(np.int32(src['control'][L_QUEUE0 + k])), 0), int(max_queue))
+        dst[name][:ln] = src[name][:ln]
+    w = 16 * ((n + TILE - 1) // TILE)
+    for name in ('active_bits', 'infected_bits'):
+        dst[name][:w] = src[name][:w]
+
+
+def _host_arrays(engine):
+    """the carried arrays of a host-memory engine as writable uint32 views"""
+    t = engine.tensors
+    n = engine.config.n_agents
+    v = lambda name: np.asarray(t[name]).view(np.uint32)
+    out = {k: v(k) for k in ('hot', 'counters', 'control', 'queue0', 'queue1', 'level1', 'active_bits', 'infected_bits')}
+    out['cold'] = v('cold').reshape(n, _eng.COLD_WORDS)
+    out['infectees'] = v('infectees').reshape(n, _eng.INLINE_INFECTEES)
+    return out
+
+
+def check_pairs(pairs, K):
+    """(dst, src) pairs as an int64 [n, 2] array; ValueError on what reina_group_clone refuses (but testing_ever)"""
+    p = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if len(p) and (p.min() < 0 or p.max() >= K):
+        raise ValueError('clone: a member index is out of range')
+    if len(np.unique(p[:, 0])) != len(p):
+        raise ValueError('clone: a destination appears twice')
+    if np.intersect1d(p[:, 0], p[:, 1]).size:
+        raise ValueError('clone: a source is also a destination')
+    return p
+
+
+def clone_group(group, pairs):
+    """Member dst of the engine group gets member src's carried state, for every (dst, src) in `pairs`: ONE launch on the
+    device (reina_group_clone), clone_state per pair for host-memory engines."""
+    engines = group.engines
+    e0 = engines[0]
+    if getattr(e0.alloc, 'torch', None) is None:
+        p = check_pairs(pairs, len(engines))
+        mq = min(e.config.max_queue for e in engines)
+        for d, s in p:
+            clone_state(_host_arrays(engines[d]), _host_arrays(engines[s]), e0.config.n_agents, mq)
+        return
+    f = getattr(e0, 'filter_f', None)
+    if f is None:
+        raise _eng.EngineError('the engine library has no particle-filter entry points (include/reina_filter.h)')
+    flat = [int(x) for pr in pairs for x in pr]
+    if len(flat) % 2:
+        raise ValueError('clone: pairs are (dst, src)')
+    arr = (ctypes.c_uint32 * max(len(flat), 1))(*[x & 0xFFFFFFFF for x in flat])
+    for e in engines:
+        e._prefetched = False
+    e0._check(f['group_clone'](group._h, arr, len(flat) // 2, e0.alloc.stream()), 'group_clone')
+
+
+# ------------------------------------------------------------------------------------------------ observation model
+
+_lgamma = np.vectorize(math.lgamma, otypes=[np.float64])
+
+
+def nb_logpmf(y, mu, r):
+    """negative-binomial log-pmf of count y with mean mu and dispersion r (variance mu + mu^2 / r), float64:
+    lgamma(y + r) - lgamma(r) - lgamma(y + 1) + r log(r / (r + mu)) + y log(mu / (r + mu))"""
+    y = np.asarray(y, dtype=np.float64)
+    mu = np.asarray(mu, dtype=np.float64)
+    r = float(r)
+    p = r / (r + mu)   # (log(mu / (r + mu)) as log1p(-p): the form scipy.stats.nbinom uses)
+    return _lgamma(y + r) - _lgamma(y + 1.0) - math.lgamma(r) + r * np.log(p) + y * np.log1p(-p)
+
+
+class ObservationModel:
+    """Negative-binomial observation model: streams = {stream: dispersion r}, stream one of STREAMS.  A simulated value is
+    the sum over ages of the stream's counter; its mean is max(value, floor).  Cumulative streams (all_detected, dead)
+    compare increments between consecutive observed dates inside the horizon (a negative observed increment counts as 0),
+    level streams (in_ward, in_icu) the level."""
+
+    def __init__(self, streams=None, floor=0.5):
+        streams = {'all_detected': 10.0} if streams is None else dict(streams)
+        if not streams:
+            raise ValueError('ObservationModel: no stream')
+        for s, r in streams.items():
+            if s not in STREAMS:
+                raise ValueError('ObservationModel: unknown stream %r (have %s)' % (s, ', '.join(STREAMS)))
+            if not (float(r) > 0 and math.isfinite(float(r))):
+                raise ValueError('ObservationModel: the dispersion of %r must be positive' % s)
+        if not float(floor) > 0:
+            raise ValueError('ObservationModel: floor must be positive')
+        self.streams = {s: float(r) for s, r in streams.items()}
+        self.floor = float(floor)
+
+    def logpmf(self, y, sim, stream):
+        return nb_logpmf(y, np.maximum(np.asarray(sim, dtype=np.float64), self.floor), self.streams[stream])
+
+
+def _as_date(x):
+    if isinstance(x, datetime):
+        return x.date()
+    if isinstance(x, date):
+        return x
+    if hasattr(x, 'date') and callable(x.date):   # pandas Timestamp
+        return x.date()
+    return date.fromisoformat(str(x)[:10])
+
+
+def align(observations, start_date, first_row, end_row, streams):
+    """{stream: (rows int64[n], values float64[n])}: the observed dates of each stream as history rows (days since
+    start_date), sorted, those in [first_row, end_row) only; missing values (NaN / None) skipped."""
+    import pandas as pd
+    df = observations if isinstance(observations, pd.DataFrame) else pd.DataFrame(observations)
+    d0 = _as_date(start_date)
+    out = {}
+    for s in streams:
+        if s not in df.columns:
+            raise ValueError('observations have no column %r' % s)
+        col = pd.to_numeric(df[s], errors='coerce')
+        rows, vals = [], []
+        for t, v in zip(df.index, col.to_numpy(dtype=np.float64)):
+            if not math.isfinite(v):
+                continue
+            d = (_as_date(t) - d0).days
+            if first_row <= d < end_row:
+                rows.append(d)
+                vals.append(v)
+        rows = np.asarray(rows, dtype=np.int64)
+        vals = np.asarray(vals, dtype=np.float64)
+        order = np.argsort(rows, kind='stable')
+        rows, vals = rows[order], vals[order]
+        if len(rows) and np.any(np.diff(rows) == 0):
+            raise ValueError('observations of %r list a date twice' % s)
+        out[s] = (rows, vals)
+    return out
+
+
+class _Scorer:
+    """Per-window log-likelihoods of the members from their history rows; carries, per cumulative stream, every member's
+    simulated value at the last observed row of the windows before (permuted with the members at a resample)."""
+
+    def __init__(self, model, aligned, K):
+        self.model = model
+        self.terms = {}
+        for s, (rows, vals) in aligned.items():
+            if STREAMS[s][1]:
+                # (row, observed increment, previous observed row): a term per observed date after the first
+                self.terms[s] = [(int(rows[j]), max(vals[j] - vals[j - 1], 0.0), int(rows[j - 1])) for j in range(1, len(rows))]
+            else:
+                self.terms[s] = [(int(rows[j]), float(vals[j]), None) for j in range(len(rows))]
+        self.rows = {s: aligned[s][0] for s in aligned}
+        self.last = {s: np.zeros(K, dtype=np.int64) for s in aligned if STREAMS[s][1]}
+
+    def score(self, hist, w0):
+        """log-likelihood [K] of the window of history rows [w0, w0 + hist.shape[1])"""
+        K, n = hist.shape[0], hist.shape[1]
+        ll = np.zeros(K, dtype=np.float64)
+        A = _eng.MAX_AGES
+        for s, terms in self.terms.items():
+            ci = _eng.C_NAMES.index(STREAMS[s][0])
+            sim = None
+            for row, y, prev in terms:
+                if not w0 <= row < w0 + n:
+                    continue
+                if sim is None:
+                    sim = hist[:, :, ci * A:(ci + 1) * A].astype(np.int64).sum(axis=2)
+                cur = sim[:, row - w0]
+                if prev is not None:
+                    cur = cur - (sim[:, prev - w0] if prev >= w0 else self.last[s])
+                ll += self.model.logpmf(y, cur, s)
+            if s in self.last:
+                rows = self.rows[s]
+                inside = rows[(rows >= w0) & (rows < w0 + n)]
+                if len(inside):
+                    if sim is None:
+                        sim = hist[:, :, ci * A:(ci + 1) * A].astype(np.int64).sum(axis=2)
+                    self.last[s] = sim[:, int(inside[-1]) - w0].copy()
+        return ll
+
+    def permute(self, ancestors):
+        for s in self.last:
+            self.last[s] = self.last[s][ancestors]
+
+
+# ------------------------------------------------------------------------------------------------ resampling
+
+def logsumexp(x):
+    x = np.asarray(x, dtype=np.float64)
+    m = np.max(x)
+    if not math.isfinite(m):
+        return m
+    return float(m + math.log(np.sum(np.exp(x - m))))
+
+
+def normalized(logw):
+    """the weights exp(logw) / sum"""
+    logw = np.asarray(logw, dtype=np.float64)
+    w = np.exp(logw - np.max(logw))
+    return w / w.sum()
+
+
+def ess(weights):
+    w = np.asarray(weights, dtype=np.float64)
+    return float(1.0 / np.sum(w * w))
+
+
+def systematic_offspring(weights, u):
+    """offspring counts [K] of systematic resampling with the uniform u in [0, 1): member i gets floor(K W_i) or
+    ceil(K W_i) copies, K in all"""
+    w = np.asarray(weights, dtype=np.float64)
+    K = len(w)
+    cs = np.cumsum(w / w.sum())
+    cs[-1] = 1.0
+    idx = np.searchsorted(cs, (float(u) + np.arange(K)) / K, side='right')
+    return np.bincount(np.minimum(idx, K - 1), minlength=K)
+
+
+def assign_in_place(counts):
+    """(ancestors [K], pairs [(dst, src)]) of offspring counts: every member with >= 1 offspring keeps its own state, the
+    surplus copies go, in ascending index order, to the members with none -- so no source is ever a destination and only
+    the members that died are written."""
+    counts = np.asarray(counts, dtype=np.int64)
+    K = len(counts)
+    anc = np.arange(K, dtype=np.int64)
+    surplus = np.repeat(np.arange(K), np.maximum(counts - 1, 0))
+    dead = np.flatnonzero(counts == 0)
+    assert len(surplus) == len(dead)
+    anc[dead] = surplus
+    return anc, [(int(d), int(s)) for d, s in zip(dead, surplus)]
+
+
+# ------------------------------------------------------------------------------------------------ the driver
+
+class FilterResult:
+    """What particle_filter returns: per window (start_day, days, loglik [K], ess, ancestors [K], resampled); log_evidence;
+    the final weights; the planner and the member Contexts (their engine group stays open for forecast(); close())."""
+
+    def __init__(self, planner, contexts, group, start_day, start_date, filter_seed):
+        self.planner = planner
+        self.contexts = contexts
+        self.group = group
+        self.start_day = start_day
+        self.start_date = _as_date(start_date)
+        self.filter_seed = filter_seed
+        self.windows = []
+        self.log_evidence = 0.0
+        self.logw = np.zeros(len(contexts), dtype=np.float64)
+        self.timings = []
+
+    @property
+    def n_particles(self):
+        return len(self.contexts)
+
+    @property
+    def weights(self):
+        return normalized(self.logw)
+
+    @property
+    def loglik(self):
+        return np.stack([w['loglik'] for w in self.windows])
+
+    @property
+    def ess(self):
+        return np.array([w['ess'] for w in self.windows])
+
+    @property
+    def ancestors(self):
+        return np.stack([w['ancestors'] for w in self.windows])
+
+    @property
+    def days(self):
+        return sum(w['days'] for w in self.windows)
+
+    def paths(self):
+        """history [K, days, COUNTER_WORDS] of every final particle, traced back through the ancestors"""
+        K = self.n_particles
+        idx = np.arange(K)
+        parts = []
+        for w in reversed(self.windows):
+            idx = w['ancestors'][idx]
+            parts.append(w['history'][idx])
+        if not parts:
+            return np.zeros((K, 0, _eng.COUNTER_WORDS), dtype=np.int32)
+        return np.concatenate(parts[::-1], axis=1)
+
+    def totals(self, attr):
+        """[K, days]: the sum over ages of a POP_ATTRS counter along every path"""
+        from .model import POP_ATTRS
+        if attr not in POP_ATTRS:
+            raise ValueError('unknown attribute %r (have %s)' % (attr, ', '.join(POP_ATTRS)))
+        ci = _eng.C_NAMES.index(attr)
+        A = _eng.MAX_AGES
+        return self.paths()[:, :, ci * A:(ci + 1) * A].astype(np.int64).sum(axis=2)
+
+    def dates(self):
+        from datetime import timedelta
+        return [self.start_date + timedelta(days=self.start_day + k) for k in range(self.days)]
+
+    def quantiles(self, attr, q=(0.05, 0.5, 0.95)):
+        """per-date quantiles of a POP_ATTRS total over the final particles, weighted by the final weights (inverted CDF):
+        a DataFrame indexed by date, one column per q"""
+        import pandas as pd
+        tot = self.totals(attr).astype(np.float64)
+        w = self.weights
+        q = [float(x) for x in np.atleast_1d(q)]
+        order = np.argsort(tot, axis=0, kind='stable')
+        out = np.zeros((tot.shape[1], len(q)))
+        for d in range(tot.shape[1]):
+            v = tot[order[:, d], d]
+            cw = np.cumsum(w[order[:, d]])
+            for j, x in enumerate(q):
+                out[d, j] = v[min(int(np.searchsorted(cw, x * cw[-1] - 1e-12, side='left')), len(v) - 1)]
+        return pd.DataFrame(out, index=self.dates(), columns=q)
+
+    def forecast(self, days):
+        """continue the group `days` days with the planner's next plan, no observations (weights unchanged); returns
+        history [K, days, COUNTER_WORDS]; paths() and quantiles() then extend over them"""
+        from . import ensemble
+        if self.group is None:
+            raise ValueError('forecast: the filter has been closed')
+        d0 = self.start_day + self.days
+        plan = self.planner.make_plan(int(days))
+        hist = ensemble.run_group_plan(self.contexts, plan, group=self.group)
+        K = self.n_particles
+        self.windows.append(dict(start_day=d0, days=int(days), loglik=np.zeros(K), ess=ess(self.weights),
+                                 ancestors=np.arange(K), resampled=False, history=hist, observed=False))
+        return hist
+
+    def close(self):
+        if self.group is not None:
+            self.group.close()
+            self.group = None
+
+
+def particle_filter(variables, n_particles, observations=None, obs_model=None, window=7, days=None, seeds=None,
+                    filter_seed=0, ess_threshold=0.5, device='cuda:0', engine_factory=None, age_counts=None, snapshot=None,
+                    comm=None):
+    """Bootstrap particle filter of `n_particles` members of the scenario `variables` (seeds[m], default 0 .. K - 1) on
+    `observations` (a DataFrame indexed by date, e.g. datasets.get_detected_cases; None: no observations, which is
+    run_group_plan of the same seeds).  Windows of `window` days; after each one the members are scored with obs_model
+    (default ObservationModel()) and resampled systematically (one uniform of numpy's PCG64(filter_seed) per resample) when
+    the ESS < ess_threshold * K.  `days` (default: up to the last observed date, else variables['simulation_days']).
+    `snapshot`: every member starts from that realised past (one group unpack, as ensemble.run_branches).  Returns a
+    FilterResult.  Sharded Contexts, K < 2, unknown streams and observations with no date inside the horizon are refused
+    (ValueError; `comm`, a sharded population's communicator, is accepted only to be refused the same way); a failing
+    member raises SimulationFailed."""
+    from . import ensemble, simulation
+    from . import snapshot as _snap
+    K = int(n_particles)
+    if comm is not None:
+        raise ValueError('particle_filter: sharded Contexts are not filtered')
+    if K < 2:
+        raise ValueError('particle_filter: at least 2 particles')
+    seeds = list(range(K)) if seeds is None else [int(s) for s in seeds]
+    if len(seeds) != K:
+        raise ValueError('particle_filter: one seed per particle')
+    window = int(window)
+    if window < 1:
+        raise ValueError('particle_filter: window must be at least 1 day')
+    if not 0.0 <= float(ess_threshold) <= 1.0:
+        raise ValueError('particle_filter: ess_threshold is a share of K in [0, 1]')
+    model = None
+    if observations is not None:
+        model = obs_model if obs_model is not None else ObservationModel()
+        if not isinstance(model, ObservationModel):
+            model = ObservationModel(dict(model))
+    ipc = None if snapshot is not None else 'auto'
+    mk = lambda sd: simulation.make_context(variables, age_counts=age_counts, seed=sd, device=device,
+                                            engine_factory=engine_factory, ipc=ipc)
+    planner = mk(seeds[0])
+    if planner.n_shards != 1 or planner.always_collective:
+        raise ValueError('particle_filter: sharded Contexts are not filtered')
+    if snapshot is not None:
+        planner.restore(snapshot, engine_state=False)
+    start_day = int(planner.day)
+    if days is None:
+        if observations is not None:
+            al = align(observations, planner.start_date, start_day, 1 << 30, model.streams)
+            last = max([int(r[-1]) for r, _ in al.values() if len(r)], default=start_day - 1)
+            days = last + 1 - start_day
+        else:
+            days = int(variables['simulation_days']) - start_day
+    days = int(days)
+    if days < 1:
+        raise ValueError('particle_filter: nothing to run (days = %d)' % days)
+    scorer = None
+    if observations is not None:
+        aligned = align(observations, planner.start_date, start_day, start_day + days, model.streams)
+        if not any(len(r) for r, _ in aligned.values()):
+            raise ValueError('particle_filter: no observed date inside the horizon (days %d .. %d)' % (start_day, start_day + days - 1))
+        scorer = _Scorer(model, aligned, K)
+    ctxs = [mk(sd) for sd in seeds]
+    if snapshot is not None:
+        for c in ctxs:
+            c.restore(snapshot, engine_state=False)
+    group = _eng.EngineGroup([c.engine for c in ctxs])
+    res = FilterResult(planner, ctxs, group, start_day, planner.start_date, filter_seed)
+    rng = np.random.Generator(np.random.PCG64(filter_seed))
+    try:
+        if snapshot is not None:
+            _snap.unpack_group(group, ctxs[0]._disease, snapshot.image)
+            for c in ctxs:
+                c.engine.upload_contact_tables(*c._packed_tables_for_restore(snapshot.state))
+        day = start_day
+        while day < start_day + days:
+            n = min(window, start_day + days - day)
+            t0 = time.perf_counter()
+            plan = planner.make_plan(n)
+            hist = ensemble.run_group_plan(ctxs, plan, group=group)
+            t1 = time.perf_counter()
+            ll = scorer.score(hist, day) if scorer is not None else np.zeros(K)
+            t2 = time.perf_counter()
+            res.log_evidence += logsumexp(res.logw + ll) - logsumexp(res.logw)   # log sum_i W_i exp(ll_i)
+            res.logw = res.logw + ll
+            w = res.weights
+            e = ess(w)
+            anc, pairs, resampled = np.arange(K), [], False
+            if e < float(ess_threshold) * K:
+                anc, pairs = assign_in_place(systematic_offspring(w, rng.random()))
+                res.logw = np.zeros(K)
+                resampled = True
+                if scorer is not None:
+                    scorer.permute(anc)
+            t3 = time.perf_counter()
+            if pairs:
+                clone_group(group, pairs)
+            t4 = time.perf_counter()
+            res.windows.append(dict(start_day=day, days=n, loglik=ll, ess=e, ancestors=anc, resampled=resampled,
+                                    history=hist, observed=scorer is not None))
+            res.timings.append(dict(run=t1 - t0, score=t2 - t1, resample=t3 - t2, clone=t4 - t3, pairs=len(pairs)))
+            day += n
+    except BaseException:
+        res.close()
+        raise
+    return res
