@@ -268,6 +268,7 @@ struct reina_engine {
     uint32_t exchange_words = REINA_PRESSURE_WORDS;   // int32 words of buffers.pressure a sharded population all-reduces per day
     uint32_t cur_scan_waves = 0;            // waves of the day's k_day launch (set by the first half of a day for the second)
     uint32_t group_lds_rows = 0, group_lds_crows = 0;   // representative of a group: the most distinct contact / count rows any member holds (LDS sizing)
+    uint32_t policy_lds_rows = 0, policy_lds_crows = 0;   // during a policy run (k_policy.inc): the most rows of any level of the bank -- the host does not know a member's level; 0 otherwise
     // (running independent kernels of a day on a second stream was measured on MI355X / ROCm 7.2:
     // the cross-stream event waits cost more than the overlap wins back -- HUS 0.108 -> 0.127 ms/day,
     // 50 M agents 0.315 -> 0.311 -- so independent phases share ONE launch instead: k_hosp_contacts)

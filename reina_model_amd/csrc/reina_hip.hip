@@ -536,9 +536,10 @@ int reina_set_initial_state(reina_engine_t *e, const reina_initial_state_t *ic, 
     return REINA_OK;
 }
 
-int reina_upload_contact_tables(reina_engine_t *e, const reina_contact_tables_t *t, void *stream) {
-    if (!e || !t) return REINA_E_INVALID;
-    hipStream_t s = (hipStream_t)stream;
+// What an upload derives from the caller's tables: the table-dependent parts of the parameter block `hp` and the Tables image
+// `ht` (distinct rows, guides, place groups, count rows, age blocks, uniform_meta).  reina_upload_contact_tables derives into
+// the engine's own mirrors, a policy's bank (k_policy.inc) into its entries'.
+static int derive_contact_tables(const reina_engine_t *e, const reina_contact_tables_t *t, DevParams &hp, Tables &ht) {
     const uint32_t A = e->cfg.nr_ages;
     if (t->n_ranges > REINA_MAX_RANGES) {
         g_last_error = "more than REINA_MAX_RANGES contact ranges";
@@ -553,14 +554,14 @@ int reina_upload_contact_tables(reina_engine_t *e, const reina_contact_tables_t 
         g_last_error = "a sharded engine takes at most REINA_MAX_RANGES - 1 contact ranges (the last range's pressure words carry free capacity)";
         return REINA_E_INVALID;
     }
-    std::memcpy(e->h_params.nrc, t->nr_contacts_by_age, sizeof(float) * A);
-    std::memcpy(e->h_params.tcount, t->count, sizeof(int32_t) * A);
-    std::memcpy(e->h_params.mask_p, t->mask_p, sizeof(float) * A * 8);
-    e->h_params.n_ranges = t->n_ranges;
-    std::memcpy(e->h_params.range_min, t->range_min, sizeof(t->range_min));
-    std::memcpy(e->h_params.range_max, t->range_max, sizeof(t->range_max));
+    std::memcpy(hp.nrc, t->nr_contacts_by_age, sizeof(float) * A);
+    std::memcpy(hp.tcount, t->count, sizeof(int32_t) * A);
+    std::memcpy(hp.mask_p, t->mask_p, sizeof(float) * A * 8);
+    hp.n_ranges = t->n_ranges;
+    std::memcpy(hp.range_min, t->range_min, sizeof(t->range_min));
+    std::memcpy(hp.range_max, t->range_max, sizeof(t->range_max));
     {   // distinct contact rows (entry count, thresholds, meta words): ages of one class of the matrix share a row
-        Tables &T = e->h_tables;
+        Tables &T = ht;
         uint32_t n_rows = 0;
         T.grouped = 1;
         for (uint32_t a = 0; a < A; a++) {
@@ -630,11 +631,16 @@ int reina_upload_contact_tables(reina_engine_t *e, const reina_contact_tables_t 
             T.age_block[b] = (uint8_t)a;
         }
     }
-    e->h_tables.uniform_meta = 1;
-    for (uint32_t r = 1; r < e->h_tables.n_rows && e->h_tables.uniform_meta; r++)
-        if (e->h_tables.rcount[r] != e->h_tables.rcount[0] ||
-            std::memcmp(e->h_tables.meta[r], e->h_tables.meta[0], sizeof(uint32_t) * (size_t)e->h_tables.rcount[0]) != 0)
-            e->h_tables.uniform_meta = 0;
+    ht.uniform_meta = 1;
+    for (uint32_t r = 1; r < ht.n_rows && ht.uniform_meta; r++)
+        if (ht.rcount[r] != ht.rcount[0] ||
+            std::memcmp(ht.meta[r], ht.meta[0], sizeof(uint32_t) * (size_t)ht.rcount[0]) != 0)
+            ht.uniform_meta = 0;
+    return REINA_OK;
+}
+
+// the pinned-staging, kernel-reads-host route of an upload: `hp` whole and the used rows of `ht` into d_params / d_tables
+static int stage_upload(reina_engine_t *e, const DevParams &hp, const Tables &ht, DevParams *d_params, Tables *d_tables, hipStream_t s) {
     size_t slot = e->stage.size();
     for (size_t k = 0; k < e->stage.size(); k++)
         if (hipEventQuery(e->stage_ev[k]) == hipSuccess) {
@@ -654,10 +660,10 @@ int reina_upload_contact_tables(reina_engine_t *e, const reina_contact_tables_t 
             HIP_CHECK(hipEventSynchronize(e->stage_ev[0]));
         }
     }
-    std::memcpy(&e->stage[slot]->p, &e->h_params, sizeof(DevParams));
+    std::memcpy(&e->stage[slot]->p, &hp, sizeof(DevParams));
     UploadSegs segs;
     {
-        const Tables &T = e->h_tables;
+        const Tables &T = ht;
         const uint32_t nr = T.n_rows ? T.n_rows : 1u, nc = T.n_crows ? T.n_crows : 1u;
         const size_t seg[8][2] = {
             {offsetof(Tables, thr), sizeof(T.thr[0]) * nr},
@@ -685,11 +691,17 @@ int reina_upload_contact_tables(reina_engine_t *e, const reina_contact_tables_t 
                   offsetof(Tables, meta) % 4 == 0 && offsetof(Tables, guide) % 4 == 0 && offsetof(Tables, grp) % 4 == 0 && offsetof(Tables, rcount) % 4 == 0 &&
                   offsetof(Tables, cthr) % 4 == 0 && offsetof(Tables, cguide) % 4 == 0 && offsetof(Tables, crow_of_age) % 4 == 0, "word copies");
     const uint32_t *src_w = reinterpret_cast<const uint32_t *>(dsrc);
-    hipLaunchKernelGGL(k_upload, dim3(64), dim3(256), 0, s, reinterpret_cast<uint32_t *>(e->d_params), src_w,
-                       (uint32_t)(sizeof(DevParams) / 4), reinterpret_cast<uint32_t *>(e->d_tables),
+    hipLaunchKernelGGL(k_upload, dim3(64), dim3(256), 0, s, reinterpret_cast<uint32_t *>(d_params), src_w,
+                       (uint32_t)(sizeof(DevParams) / 4), reinterpret_cast<uint32_t *>(d_tables),
                        src_w + offsetof(reina_engine::Stage, t) / 4, segs);
     HIP_CHECK(hipEventRecord(e->stage_ev[slot], s));
     return REINA_OK;
+}
+
+int reina_upload_contact_tables(reina_engine_t *e, const reina_contact_tables_t *t, void *stream) {
+    if (!e || !t) return REINA_E_INVALID;
+    if (int rc = derive_contact_tables(e, t, e->h_params, e->h_tables)) return rc;
+    return stage_upload(e, e->h_params, e->h_tables, e->d_params, e->d_tables, (hipStream_t)stream);
 }
 
 // k_day's workgroups for one engine instance: one 512-agent tile per wave (small populations) up to one
@@ -818,9 +830,11 @@ static int launch_day_main(reina_engine_t *e, const MemberRef *refs, uint32_t K,
     if (geo.xtrace) LAUNCH_DAY(e, today, REINA_PK_XCHG, k_xtrace, dim3(xchg_grid(e), K), dim3(256), 0, s, dp, 1);
     const uint32_t day_blocks = geo.day_blocks, stream_imports = geo.stream_imports;
     uint32_t lds_rows = K > 1 ? e->group_lds_rows : e->h_tables.n_rows;   // (a member stages min(its own rows, lds_rows))
+    if (e->policy_lds_rows) lds_rows = e->policy_lds_rows;   // (a policy run: the most rows of any level of its bank, k_policy.inc)
     if (lds_rows > REINA_LDS_ROWS) lds_rows = REINA_LDS_ROWS;
     if (e->lds_rows_cap && lds_rows > e->lds_rows_cap) lds_rows = e->lds_rows_cap;
     uint32_t lds_crows = K > 1 ? e->group_lds_crows : e->h_tables.n_crows;
+    if (e->policy_lds_crows) lds_crows = e->policy_lds_crows;
     if (lds_crows > REINA_LDS_CROWS) lds_crows = REINA_LDS_CROWS;
     if (e->lds_rows_cap && lds_crows > e->lds_rows_cap) lds_crows = e->lds_rows_cap;
     // a vaccination programme: its pass over the agents comes after the test queue and before the stream
@@ -1278,8 +1292,11 @@ int reina_group_upload_contact_tables(reina_group_t *g, const reina_contact_tabl
     return REINA_OK;
 }
 
-int reina_group_run_days(reina_group_t *g, const reina_day_t *days, uint32_t n_days, int32_t *const *history_bases,
-                         void *stream) {
+// a policy's launch ahead of a day's opening (k_policy.inc)
+static int policy_launch_day(struct reina_policy *p, const reina_day_t &dp, hipStream_t s);
+
+static int group_run_days(reina_group_t *g, const reina_day_t *days, uint32_t n_days, int32_t *const *history_bases,
+                          void *stream, struct reina_policy *policy) {
     if (!g || !days) return REINA_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const uint32_t K = (uint32_t)g->members.size();
@@ -1301,7 +1318,8 @@ int reina_group_run_days(reina_group_t *g, const reina_day_t *days, uint32_t n_d
     for (uint32_t d = 0; d < n_days; d++) {
         reina_day_t dp = days[d];
         dp.history_row = nullptr;
-        int rc = launch_day_begin(e0, g->d_refs, K, dp, d, s);
+        int rc = policy ? policy_launch_day(policy, dp, s) : REINA_OK;
+        if (rc == REINA_OK) rc = launch_day_begin(e0, g->d_refs, K, dp, d, s);
         if (rc == REINA_OK) rc = launch_day_end(e0, g->d_refs, K, dp, s);
         if (rc) {
             e0->h_ref = own_ref;
@@ -1314,6 +1332,11 @@ int reina_group_run_days(reina_group_t *g, const reina_day_t *days, uint32_t n_d
         m->cur_scan_waves = e0->cur_scan_waves;
     }
     return REINA_OK;
+}
+
+int reina_group_run_days(reina_group_t *g, const reina_day_t *days, uint32_t n_days, int32_t *const *history_bases,
+                         void *stream) {
+    return group_run_days(g, days, n_days, history_bases, stream, nullptr);
 }
 
 int reina_read_counters(reina_engine_t *e, int32_t *out_host, void *stream) {
@@ -1412,3 +1435,6 @@ int reina_profile_read(reina_engine_t *e, double *scan_ms_total, uint64_t *scan_
 
 // the particle filter's in-group clone (include/reina_filter.h): kernel and entry point
 #include "k_filter.inc"
+
+// triggered interventions (include/reina_policy.h): the deciding kernel and entry points
+#include "k_policy.inc"

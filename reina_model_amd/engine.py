@@ -351,6 +351,9 @@ class Engine:
         # the particle filter's in-group clone (include/reina_filter.h): likewise
         from .filtering import bind_filter_abi
         self.filter_f = bind_filter_abi(lib, prefix)
+        # triggered interventions (include/reina_policy.h): likewise
+        from .policy import bind_policy_abi
+        self.policy_f = bind_policy_abi(lib, prefix)
         self.config = config
         self._h = ctypes.c_void_p()
         self._check(self.f['create'](ctypes.byref(config), ctypes.byref(disease), ctypes.byref(self._h)), 'create')

@@ -24,7 +24,7 @@ from . import simulation
 from .filtering import particle_filter  # noqa: F401  (conditioned ensembles: reina_model_amd/filtering.py)
 
 
-def run_group_plan(contexts, plan, record_history=True, member_plans=None, group=None):
+def run_group_plan(contexts, plan, record_history=True, member_plans=None, group=None, policy=None):
     """Execute `plan` (Context.make_plan) for all `contexts` as one engine group.  Returns
     history[len(contexts), days, COUNTER_WORDS] (host) or None.
 
@@ -33,8 +33,20 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
     of `plan` while every member gets its own contact tables at each table change.
 
     `group`: an engine.EngineGroup of exactly these contexts' engines, made by the caller (run_branches restores its members
-    with one launch first); it stays open.  Otherwise a group is made for the run and closed after it."""
+    with one launch first); it stays open.  Otherwise a group is made for the run and closed after it.
+
+    `policy` (policy.Policy; the plan made with it, make_plan(days, policy=...)): every member reacts to its own counters --
+    k_policy ahead of every day, one bank of level tables for the whole group.  Every member starts at level 0 with an empty
+    ring; its levels end up in `context.policy_levels`, its mobility factors in `context.mobility_history`."""
     from . import engine as _eng
+    from . import policy as _pol
+    if policy is not None:
+        if member_plans is not None:
+            raise ValueError('run_group_plan: a policy and member_plans (a sweep) cannot be combined')
+        if plan.get('policy') is not policy or plan.get('policy_banks') is None:
+            raise ValueError('run_group_plan: the plan must be made with the policy (make_plan(days, policy=...))')
+        for c in contexts:
+            _pol.check_capable(c)
     import os as _os, time as _time
     _T = [] if _os.environ.get('REINA_ENS_TIMING') else None   # (diagnostic: where a group run's wall time goes, tools/ens_first_run2.py)
     def _t(name):
@@ -54,7 +66,13 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
     hist = a.zeros(K * days * _eng.COUNTER_WORDS, np.int32) if record_history else None
     row = 4 * _eng.COUNTER_WORDS
     done = 0
+    dev = _pol.DevicePolicy(policy, contexts[0].start_date, group=group) if policy is not None else None
     for si, (tables, arr, n) in enumerate(plan['segments']):
+        if dev is not None:
+            dev.upload_bank(plan['policy_banks'][si][0])
+            dev.run_day_array(arr, n, [a.ptr(hist) + row * (m * days + done) for m in range(K)] if record_history else None)
+            done += n
+            continue
         if member_plans is not None:
             for c, mp in zip(contexts, member_plans):
                 if mp['segments'][si][0] is not None:
@@ -65,8 +83,17 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
         group.run_day_array(arr, n, ptrs)
         done += n
     _t('issued')
+    if dev is not None:
+        trace = dev.read_trace(plan['start_day'], days)   # (the run's wait; the members' host-side table mirrors follow their levels)
+        dev.close()
+        seg_of_day, factors = _pol.plan_segments_of_days(plan), [b[1] for b in plan['policy_banks']]
     for m, c in enumerate(contexts):
-        c.mobility_history = (member_plans[m] if member_plans is not None else plan)['mobility_history']
+        if dev is not None:
+            c.day = plan['start_day']
+            first_value = _pol._first_mobility(c, plan['mobility_history'][0]) if days else 0.0
+            _pol._finish(c, first_value, trace[m, :, 0], seg_of_day, factors, plan['start_day'] + days)
+        else:
+            c.mobility_history = (member_plans[m] if member_plans is not None else plan)['mobility_history']
         c.day = plan['start_day'] + days
     out = None
     if record_history:
@@ -191,16 +218,40 @@ def run_ensemble(variables, seeds, days, age_counts=None, device='cuda:0', threa
     return np.stack(out)
 
 
+def run_policy_ensemble(variables, seeds, days, policy, age_counts=None, device='cuda:0', engine_factory=None, ipc='auto',
+                        interventions=None):
+    """One simulation per seed for `days` days, every member reacting to its own counters under `policy` (policy.Policy), all
+    as ONE engine group.  Returns (history[K, days, COUNTER_WORDS], levels[K, days], contexts).  An engine library without the
+    policy entry points runs the members one after the other by policy.run_host_driven."""
+    from . import policy as _pol
+    seeds = list(seeds)
+    mk = lambda sd: simulation.make_context(variables, age_counts=age_counts, seed=sd, device=device, interventions=interventions,
+                                            engine_factory=engine_factory, ipc=ipc)
+    ctxs = [mk(sd) for sd in seeds]
+    if ctxs[0].engine.policy_f is None:
+        hist = np.stack([_pol.run_host_driven(c, policy, days) for c in ctxs])
+    else:
+        planner = mk(seeds[0])
+        plan = planner.make_plan(days, policy=policy)
+        del planner
+        hist = run_group_plan(ctxs, plan, policy=policy)
+    return hist, np.stack([c.policy_levels for c in ctxs]), ctxs
+
+
 def run_branches(snap, variables, seeds, days, member_variables=None, age_counts=None, device='cuda:0', engine_factory=None,
-                 interventions=None):
+                 interventions=None, policy=None):
     """Conditional ensemble: K = len(seeds) futures of ONE realised past.  Every member is a Context of `variables` (or of
     member_variables[m]) restored from `snap` (snapshot.Snapshot) -- on the device all K by one launch
     (reina_group_snap_unpack) -- with its own seed, then `days` days are run as one engine group (run_group_plan).
     member_variables follows run_sweep's rule: the members may differ only in the values of their mobility and mask
     interventions.  `interventions`: intervention tuples of every member instead of its variables' scenario (make_context).
+    `policy` (policy.Policy): every future reacts to its own course from the snapshot's day on (levels in
+    contexts[m].policy_levels); not together with member_variables.
     Returns (history[K, days, COUNTER_WORDS], contexts)."""
     from . import engine as _eng
     from . import snapshot as _snap
+    if policy is not None and member_variables is not None:
+        raise ValueError('run_branches: a policy and member_variables cannot be combined')
     vs = list(member_variables) if member_variables is not None else [variables] * len(seeds)
     if len(vs) != len(seeds):
         raise ValueError('run_branches: one member_variables entry per seed')
@@ -212,7 +263,9 @@ def run_branches(snap, variables, seeds, days, member_variables=None, age_counts
         planner = simulation.make_context(v, age_counts=age_counts, seed=sd, device=device, engine_factory=engine_factory,
                                           interventions=interventions)
         planner.restore(snap, engine_state=False)
-        plans.append(planner.make_plan(days))
+        if policy is not None:
+            planner._packed_tables_for_restore(snap.state)   # (the mask shares of the snapshot's last upload: level tables start from them)
+        plans.append(planner.make_plan(days, policy=policy))
         del planner
     for k, p in enumerate(plans[1:], 1):
         if p is not plans[0] and not _same_day_descriptors(plans[0], p):
@@ -230,7 +283,7 @@ def run_branches(snap, variables, seeds, days, member_variables=None, age_counts
         for c in ctxs:
             c.engine.upload_contact_tables(*c._packed_tables_for_restore(snap.state))
         member_plans = plans if member_variables is not None else None
-        hist = run_group_plan(ctxs, plans[0], member_plans=member_plans, group=group)
+        hist = run_group_plan(ctxs, plans[0], member_plans=member_plans, group=group, policy=policy)
     finally:
         group.close()
     return hist, ctxs

@@ -227,13 +227,18 @@ class Context:
     """MI355X-native agent engine with the reference `Context` protocol (main.pyx:1746-2101)."""
 
     def __init__(self, population_params, healthcare_params, disease_params, start_date,
-                 random_seed=4321, device='cuda:0', engine_factory=None, comm=None, strict=False):
+                 random_seed=4321, device='cuda:0', engine_factory=None, comm=None, strict=False, policy=None):
         """`comm` (sharding.TorchComm or compatible: .rank, .world, .all_reduce_sum/max) makes this
         Context one shard of a population split over comm.world engine instances; population,
-        beds, ICU units and import / vaccination quotas given here are the GLOBAL ones."""
+        beds, ICU units and import / vaccination quotas given here are the GLOBAL ones.
+        `policy` (policy.Policy): run() and run_plan() take the policy route (reina_model_amd/policy.py)."""
         from .sharding import split_count, split_population
         self.comm = comm
         self.strict = bool(strict)   # iterate() raises on the day of a problem (main.pyx:2017-2018)
+        self.policy = policy
+        self.policy_levels = None    # after a policy run: the level in force on each of its days
+        if policy is not None and comm is not None and (comm.world > 1 or getattr(comm, 'always_collective', False)):
+            raise ValueError('policy: sharded Contexts are refused (the signal would need the all-reduce of the shards)')
         # testing aid: take the begin / all-reduce / end path even with a single shard
         self.always_collective = bool(comm is not None and getattr(comm, 'always_collective', False))
         self._direct = getattr(comm, 'direct', None) if comm is not None else None
@@ -621,11 +626,17 @@ class Context:
         if self.n_shards == 1 and not self.always_collective:
             self.engine.prefetch_counters()   # the next generate_state() finds them on the host
 
-    def make_plan(self, days):
+    def make_plan(self, days, policy=None):
         """Host part of `days` consecutive days, done once: the intervention schedule turned into
         day descriptors, cut into stretches of unchanged contact tables.  A plan does not depend
         on the random seed, so one plan can drive every member of a Monte-Carlo ensemble
-        (reina_model_amd/ensemble.py).  Advances this Context's host-side state by `days`."""
+        (reina_model_amd/ensemble.py).  Advances this Context's host-side state by `days`.
+        `policy` (policy.Policy): the plan also carries, per stretch, the tables and mobility factor of every level
+        (plan['policy_banks'][stretch] = (tables[level], factors[level]); the first stretch begins with the plan)."""
+        if policy is not None:
+            from . import policy as _pol
+            _pol.check_capable(self)
+        banks = []
         segments = []   # (packed tables or None, ctypes Day array, n)
         start_day = self.day
         self._planner = True
@@ -640,17 +651,26 @@ class Context:
                     segments.append((tables, (_eng.Day * len(pending))(*pending), len(pending)))
                     pending = []
                 tables = self._packed_tables()
+            if policy is not None and (changed or not banks):
+                banks.append(_pol.build_bank(self, policy))
             pending.append(d)
             self.day += 1
         if pending:
             segments.append((tables, (_eng.Day * len(pending))(*pending), len(pending)))
-        return dict(segments=segments, days=days, mobility_history=mobility, start_day=start_day)
+        plan = dict(segments=segments, days=days, mobility_history=mobility, start_day=start_day)
+        if policy is not None:
+            plan.update(policy=policy, policy_banks=banks)
+        return plan
 
     def run_plan(self, plan, record_history=True):
         """Execute a plan made by make_plan (of this Context or of another one with the same
         scenario).  Returns history[days, COUNTER_WORDS] like run().  The scenario's host-side state
         (intervention cursor, contact matrix) advances only in the Context that MADE the plan:
         continue a replayed simulation with further plans of that same planner."""
+        if self.policy is not None:
+            from . import policy as _pol
+            self._replayed = True
+            return _pol.run_plan_device(self, plan, record_history)
         days = plan['days']
         a = self.engine.alloc
         self._replayed = True
@@ -729,7 +749,14 @@ class Context:
         tables (the loop of calc/simulation.py:194-270 without per-day host round trips).
         Returns history[days, COUNTER_WORDS] (row d = counters BEFORE day d ran) as a host array,
         or None; `self.mobility_history[d]` is the mobility factor generate_state() would have
-        reported on that day."""
+        reported on that day.  With a policy attached (Context(..., policy=p)): the policy route -- k_policy ahead of every day
+        on the GPU, policy.run_host_driven on an engine library without the policy entry points -- which also sets
+        `self.policy_levels`."""
+        if self.policy is not None:
+            from . import policy as _pol
+            if self.engine.policy_f is None:
+                return _pol.run_host_driven(self, self.policy, days, record_history)
+            return _pol.run_device(self, days, record_history)
         if self._in_stream or (self.n_shards == 1 and not self.always_collective):
             return self._run_streamed(days, record_history)
         a = self.engine.alloc
@@ -848,6 +875,8 @@ class Context:
     def snapshot(self):
         """The simulation as it stands between two days: a snapshot.Snapshot that Context.restore() continues from."""
         from . import snapshot as _snap
+        if self.policy is not None:
+            raise ValueError('snapshot: a Context with a policy is refused (the policy state lives outside the engine state)')
         self._check_snapshot_capable('snapshot')
         counters = self._read_counters_global()
         if int(counters[_eng.C_NR * _eng.MAX_AGES + _eng.S_PROBLEM]) != 0:

@@ -53,12 +53,12 @@ def create_disease_params(variables):
 
 
 def make_context(variables, age_counts=None, seed=None, interventions=None, device='cuda:0',
-                 engine_factory=None, comm=None, ipc=None, strict=False, snapshot=None):
+                 engine_factory=None, comm=None, ipc=None, strict=False, snapshot=None, policy=None):
     """Build a Context the way calc/simulation.py:148-180 does.  `ipc`: an InitialPopulationCondition,
     a dict of its fields, None (no initial condition), or 'auto' = what simulate_individuals passes,
     datasets.get_initial_population_condition(variables) (calc/simulation.py:152).
     `snapshot` (snapshot.Snapshot): the Context continues from it (Context.restore); no initial condition is applied, the
-    state is replaced."""
+    state is replaced.  `policy` (policy.Policy): triggered interventions -- run() takes the policy route."""
     if snapshot is not None:
         ipc = None
     if isinstance(ipc, str) and ipc == 'auto':
@@ -77,7 +77,7 @@ def make_context(variables, age_counts=None, seed=None, interventions=None, devi
     hc = dict(hospital_beds=variables['hospital_beds'], icu_units=variables['icu_units'])
     ctx = model.Context(pop_params, hc, create_disease_params(variables), variables['start_date'],
                         random_seed=variables['random_seed'] if seed is None else seed,
-                        device=device, engine_factory=engine_factory, comm=comm, strict=strict)
+                        device=device, engine_factory=engine_factory, comm=comm, strict=strict, policy=policy)
     if interventions is None:
         ivs = get_active_interventions(variables)
     else:
@@ -91,13 +91,15 @@ def make_context(variables, age_counts=None, seed=None, interventions=None, devi
 
 
 def simulate_individuals(variables=None, step_callback=None, callback_day_interval=1, device='cuda:0',
-                         engine_factory=None, age_counts=None):
+                         engine_factory=None, age_counts=None, policy=None):
+    """`policy` (policy.Policy): the run reacts to its own counters; df's mobility_limitation follows the levels and df gets a
+    `policy_level` column (the level in force on each date)."""
     import pandas as pd
     if variables is None:
         variables = copy_variables()
     t0 = time.perf_counter()
     ctx = make_context(variables, age_counts=age_counts, device=device, engine_factory=engine_factory,
-                       ipc=datasets.get_initial_population_condition(variables))   # calc/simulation.py:152
+                       ipc=datasets.get_initial_population_condition(variables), policy=policy)   # calc/simulation.py:152
     start_date = date.fromisoformat(variables['start_date'])
     days = variables['simulation_days']
     age_groups = ctx.age_group_labels
@@ -109,14 +111,20 @@ def simulate_individuals(variables=None, step_callback=None, callback_day_interv
     if step_callback is None:   # no progress reports wanted: one run, frames for all days at once
         last = time.perf_counter()
         hist = ctx.run(days)
-        return _frames_from_history(ctx, hist, ctx.mobility_history, start_date, (time.perf_counter() - last) * 1000 / days)
+        df, adf = _frames_from_history(ctx, hist, ctx.mobility_history, start_date, (time.perf_counter() - last) * 1000 / days)
+        if policy is not None:
+            df['policy_level'] = np.asarray(ctx.policy_levels, dtype=np.int64)
+        return df, adf
 
     done = 0
     stretch = max(1, int(callback_day_interval))
     last = time.perf_counter()
+    levels = []
     while done < days:
         n = min(stretch, days - done)
         hist = ctx.run(n)
+        if policy is not None:
+            levels += [int(x) for x in ctx.policy_levels]
         now = time.perf_counter()
         ms_per_day = (now - last) * 1000 / n
         last = now
@@ -136,6 +144,8 @@ def simulate_individuals(variables=None, step_callback=None, callback_day_interv
         if not step_callback(df):
             raise ExecutionInterrupted()
     df = pd.DataFrame(rows, index=date_index, columns=cols).astype(np.float64).astype(object)
+    if policy is not None:
+        df['policy_level'] = np.asarray(levels, dtype=np.int64)
     adf = pd.DataFrame(
         ag_array.flatten(),
         index=pd.MultiIndex.from_product([date_index, POP_ATTRS, age_groups], names=['date', 'attr', 'age_group']),
