@@ -1,0 +1,485 @@
+// reina_hip.hip part: the dated transmission log (include/reina_txlog.h; DESIGN.md section 6f).
+// Included at the end of reina_hip.hip (it uses the host helpers, the group and k_transmission.inc's tx_count above).
+//
+// Three kernels, each bound by memory traffic:
+//   k_txlog_begin   streams the hot words (16 bytes a lane) and writes every log word.
+//   k_txlog_day     ONE launch a day, queued behind the day's last launch.  It streams the ACTIVE bit plane (N / 8 bytes) in the
+//                   512-agent tiles of 16 words that k_day's sparse stream uses, one tile a wave: lane l looks at agent
+//                   64 j + l of the tile in round j, so the hot words of a dense tile are fetched coalesced.  Two forms of the
+//                   update, chosen per launch:
+//                     by_hot = 0  reads the log word of every active agent and applies the definition to it;
+//                     by_hot = 1  decides from the hot word alone -- INCUBATION with the day in bits 24-31: the agent was infected
+//                                 today, a full-word store; ILLNESS with day + 1 there: its onset was today, a 16-bit store of the
+//                                 upper half -- and never reads the log.  tests/test_txlog.py keeps checked, on oracle B, that
+//                                 the two coincide on simulated states.  The host takes by_hot = 0 on the first day a log
+//                                 records and on any day that does not follow the last one recorded: the agents an initial
+//                                 condition leaves incubating carry day 0 in bits 24-31 and are BEFORE, not "infected on day 0".
+//   k_txlog_report  streams hot + log, gathers the cold record of infected agents and hot + log of their infectors; the interval
+//                   histograms and the scalars are counted in LDS and flushed once per workgroup; the tables indexed by day
+//                   (too large for LDS at 4096 days) go to global atomics aggregated in the wave: the lanes that share the first
+//                   lane's cell add once (agents are sorted by age and an epidemic's days are few: most of a wave's lanes do).
+// GROUP: the member is element blockIdx.y of the group's member table (MEMBER_OF_LAUNCH), its log words and report block the
+// blockIdx.y-th of the log's; otherwise the one engine by value.  One lane owns an agent: no atomics on the log, no fences (a
+// kernel boundary lies on either side of every launch).
+#include "../../include/reina_txlog.h"
+
+#define TXL_THREADS 256
+#define TXL_TILE 512u
+#define TXL_NONE ((uint32_t)REINA_TXLOG_NONE)
+#define TXL_BEFORE ((uint32_t)REINA_TXLOG_BEFORE)
+static_assert(REINA_MAX_DAYS < REINA_TXLOG_BEFORE, "day numbers lie below the codes");
+static_assert(REINA_TXLOG_FIXED_WORDS == 1312u && REINA_TXLOG_DAY_WORDS == 80u, "report layout");
+static_assert(REINA_TXLOG_VARIANTS == REINA_MAX_VARIANTS && REINA_TXLOG_MAX_GROUPS == REINA_TX_MAX_GROUPS, "RH_VARIANT has two bits; the groups are the tree reports'");
+
+struct TxlArgs {
+    uint32_t n_agents, nr_ages, n_days, pad_;
+    int32_t age_start[REINA_MAX_AGES + 1];
+    uint8_t group[REINA_MAX_AGES];
+};
+
+__host__ __device__ __forceinline__ uint32_t txl_begin_word(uint32_t w) {
+    const uint32_t st = RH_STATE(w);
+    return (st >= RS_ILLNESS ? TXL_BEFORE : TXL_NONE) << 16 | (st != RS_SUSCEPTIBLE ? TXL_BEFORE : TXL_NONE);
+}
+
+// the log is padded to whole tiles (its words beyond n_agents: NONE | NONE, never read back); the hot words are not
+template <bool GROUP>
+__global__ __launch_bounds__(TXL_THREADS) void k_txlog_begin(const MemberRef *M_, const MemberRef one_, uint32_t *log, size_t stride, uint32_t N) {
+    MEMBER_OF_LAUNCH;
+    const GAS uint32_t *hot = (const GAS uint32_t *)mref_.B.hot;
+    GAS uint32_t *L = (GAS uint32_t *)log + (GROUP ? (size_t)blockIdx.y * stride : 0u);
+    const uint32_t quads = (N + 3u) / 4u;
+    for (uint32_t q = blockIdx.x * TXL_THREADS + threadIdx.x; q < quads; q += gridDim.x * TXL_THREADS) {
+        const uint32_t i = 4u * q;
+        v4u_ w;
+        if (i + 3u < N) {
+            w = *reinterpret_cast<const GAS v4u_ *>(hot + i);
+        } else {
+            w.x = hot[i];
+            w.y = i + 1u < N ? hot[i + 1u] : 0u;
+            w.z = i + 2u < N ? hot[i + 2u] : 0u;
+            w.w = 0u;
+        }
+        v4u_ o;
+        o.x = txl_begin_word(w.x);
+        o.y = txl_begin_word(w.y);
+        o.z = txl_begin_word(w.z);
+        o.w = txl_begin_word(w.w);
+        *reinterpret_cast<GAS v4u_ *>(L + i) = o;
+    }
+}
+
+// four waves a workgroup, one tile a wave and round, the tiles strided over the grid
+template <bool GROUP>
+__global__ __launch_bounds__(TXL_THREADS) void k_txlog_day(const MemberRef *M_, const MemberRef one_, uint32_t *log, size_t stride, uint32_t N, uint32_t day,
+                                                           uint32_t by_hot) {
+    MEMBER_OF_LAUNCH;
+    const GAS uint32_t *hot = (const GAS uint32_t *)mref_.B.hot;
+    const GAS uint32_t *plane = (const GAS uint32_t *)mref_.B.active_bits;
+    GAS uint32_t *L = (GAS uint32_t *)log + (GROUP ? (size_t)blockIdx.y * stride : 0u);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t tiles = (N + TXL_TILE - 1u) / TXL_TILE;
+    const uint32_t d8 = day & 0xFFu, o8 = (day + 1u) & 0xFFu;
+    for (uint32_t t = blockIdx.x * (TXL_THREADS / 64u) + wave; t < tiles; t += gridDim.x * (TXL_THREADS / 64u)) {
+        const uint32_t wd = plane[t * 16u + (lane & 15u)];   // (the plane holds whole tiles: REINA_BITS_WORDS)
+        if (!__ballot(wd != 0u)) continue;
+        uint32_t w[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t bits = (uint32_t)__shfl((int)wd, 2 * j + (int)(lane >> 5));
+            const uint32_t i = t * TXL_TILE + (uint32_t)j * 64u + lane;
+            w[j] = ((bits >> (lane & 31u)) & 1u) && i < N ? hot[i] : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t i = t * TXL_TILE + (uint32_t)j * 64u + lane, st = RH_STATE(w[j]);
+            if (st == RS_SUSCEPTIBLE) continue;
+            if (by_hot) {
+                if (st == RS_INCUBATION && (w[j] >> 24) == d8)
+                    L[i] = TXL_NONE << 16 | day;
+                else if (st == RS_ILLNESS && (w[j] >> 24) == o8)
+                    reinterpret_cast<GAS uint16_t *>(L)[2u * i + 1u] = (uint16_t)day;
+            } else {
+                const uint32_t lw = L[i];
+                uint32_t nw = lw;
+                if ((lw & 0xFFFFu) == TXL_NONE) nw = (nw & 0xFFFF0000u) | day;
+                if ((lw >> 16) == TXL_NONE && st >= RS_ILLNESS) nw = (nw & 0xFFFFu) | day << 16;
+                if (nw != lw) L[i] = nw;
+            }
+        }
+    }
+}
+
+// val into cell `key` of a table in global memory for every lane with key >= 0: the lanes that share the first such lane's
+// cell add their sum once.  Called by whole waves.
+__device__ __forceinline__ void txl_add(GAS unsigned long long *tab, int key, unsigned long long val) {
+    const uint64_t act = __ballot(key >= 0);
+    if (!act) return;
+    const int lead = __ffsll((unsigned long long)act) - 1;
+    const int lk = __shfl(key, lead);
+    const bool same = key == lk;
+    unsigned long long s = same ? val : 0ull;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)s, off), hi = (uint32_t)__shfl_xor((int)(uint32_t)(s >> 32), off);
+        s += ((unsigned long long)hi << 32) | lo;
+    }
+    if (same) {
+        if ((int)(threadIdx.x & 63u) == lead && s) atomicAdd(&tab[lk], s);
+    } else if (key >= 0 && val) {
+        atomicAdd(&tab[key], val);
+    }
+}
+
+__device__ __forceinline__ int txl_clip(int x, int hi) { return x < 0 ? 0 : (x > hi ? hi : x); }
+
+// 256 threads, tiles of 512 agents (two per thread), the workgroup's tiles strided over the grid
+template <bool GROUP>
+__global__ __launch_bounds__(TXL_THREADS) void k_txlog_report(const MemberRef *M_, const MemberRef one_, const uint32_t *log, size_t stride,
+                                                              uint64_t *report, const TxlArgs a) {
+    __shared__ uint32_t s_h[REINA_TXLOG_SCALARS];   // the interval histograms and the link phases, at the block's own offsets
+    __shared__ uint32_t s_c[REINA_TXLOG_S_NR];
+    __shared__ int32_t s_as[REINA_MAX_AGES + 1];
+    __shared__ uint8_t s_grp[REINA_MAX_AGES];
+    MEMBER_OF_LAUNCH;
+    const GAS uint32_t *hot = (const GAS uint32_t *)mref_.B.hot;
+    const GAS reina_cold_t *cold = (const GAS reina_cold_t *)mref_.B.cold;
+    const GAS uint32_t *L = (const GAS uint32_t *)log + (GROUP ? (size_t)blockIdx.y * stride : 0u);
+    GAS unsigned long long *R = (GAS unsigned long long *)report + (GROUP ? (size_t)blockIdx.y * REINA_TXLOG_REPORT_WORDS(a.n_days) : 0u);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    for (uint32_t k = tid; k < REINA_TXLOG_SCALARS; k += TXL_THREADS) s_h[k] = 0u;
+    if (tid < REINA_TXLOG_S_NR) s_c[tid] = tid == REINA_TXLOG_S_FIRST_DAY ? 0xFFFFFFFFu : 0u;
+    if (tid <= REINA_MAX_AGES) s_as[tid] = a.age_start[tid];
+    if (tid < REINA_MAX_AGES) s_grp[tid] = a.group[tid];
+    __syncthreads();
+    const uint32_t N = a.n_agents, D = a.n_days, tiles = (N + TXL_TILE - 1u) / TXL_TILE;
+    const int top = (int)a.nr_ages - 1;
+    GAS unsigned long long *inc_t = R + REINA_TXLOG_INCIDENCE(D), *ons_t = R + REINA_TXLOG_ONSETS(D), *coh_t = R + REINA_TXLOG_COHORT(D);
+    for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        uint32_t idx[2], w[2], lw[2];
+        bool inf[2];
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            idx[j] = t * TXL_TILE + (uint32_t)j * TXL_THREADS + tid;
+            w[j] = idx[j] < N ? hot[idx[j]] : 0u;
+            lw[j] = idx[j] < N ? L[idx[j]] : 0u;
+            inf[j] = RH_STATE(w[j]) != RS_SUSCEPTIBLE;
+        }
+        if (!__ballot(inf[0] || inf[1])) continue;
+        int32_t src[2] = {-1, -1};
+        uint32_t n[2] = {0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            if (inf[j]) {
+                const v2u_ c = *reinterpret_cast<const GAS v2u_ *>(&cold[idx[j]].infector);   // infector, n_infected
+                src[j] = (int32_t)c.x;
+                n[j] = c.y;
+            }
+        }
+        uint32_t sw[2] = {0u, 0u}, sl[2] = {0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+            if (inf[j] && src[j] >= 0 && (uint32_t)src[j] < N && (uint32_t)src[j] != idx[j]) {
+                sw[j] = hot[src[j]];
+                sl[j] = L[src[j]];
+            }
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const uint32_t i = idx[j], v = RH_VARIANT(w[j]);
+            const uint32_t ti = lw[j] & 0xFFFFu, oi = lw[j] >> 16;
+            const bool tk = inf[j] && ti < TXL_BEFORE, ok = inf[j] && oi < TXL_BEFORE;
+            const bool root = inf[j] && src[j] == -1;
+            const bool linked = inf[j] && !root && RH_STATE(sw[j]) != RS_SUSCEPTIBLE;   // (sw = 0 for an infector out of range or itself)
+            const bool bad = inf[j] && !root && !linked;
+            const uint32_t ts = sl[j] & 0xFFFFu, os = sl[j] >> 16;
+            const bool tsk = linked && ts < TXL_BEFORE, osk = linked && os < TXL_BEFORE;
+            const bool both = tk && tsk;
+            // the scalars: one LDS atomic a wave and kind
+            const uint32_t oor = (tk && ti >= D ? 1u : 0u) + (ok && oi >= D ? 1u : 0u);
+            const uint32_t cnt[9] = {(uint32_t)__popcll(__ballot(inf[j])), (uint32_t)__popcll(__ballot(tk)),
+                                     (uint32_t)__popcll(__ballot(inf[j] && ti == TXL_BEFORE)), (uint32_t)__popcll(__ballot(ok)),
+                                     (uint32_t)__popcll(__ballot(linked)), (uint32_t)__popcll(__ballot(both)),
+                                     (uint32_t)__popcll(__ballot(both && ti <= ts)),
+                                     (uint32_t)__popcll(__ballot(oor >= 1u)) + (uint32_t)__popcll(__ballot(oor == 2u)),
+                                     (uint32_t)__popcll(__ballot(bad))};
+            uint32_t lo = tk ? ti : 0xFFFFFFFFu, hi = tk ? ti : 0u;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const uint32_t a_ = (uint32_t)__shfl_xor((int)lo, off), b_ = (uint32_t)__shfl_xor((int)hi, off);
+                lo = a_ < lo ? a_ : lo;
+                hi = b_ > hi ? b_ : hi;
+            }
+            if (lane == 0) {
+                const uint32_t at[9] = {REINA_TXLOG_S_INFECTED, REINA_TXLOG_S_DATED, REINA_TXLOG_S_BEFORE, REINA_TXLOG_S_WITH_ONSET,
+                                        REINA_TXLOG_S_LINKS, REINA_TXLOG_S_LINKS_DATED, REINA_TXLOG_S_GENERATION_NONPOSITIVE,
+                                        REINA_TXLOG_S_OUT_OF_RANGE, REINA_TXLOG_S_BAD_LINKS};
+#pragma unroll
+                for (int k = 0; k < 9; k++)
+                    if (cnt[k]) atomicAdd(&s_c[at[k]], cnt[k]);
+                if (cnt[1]) {
+                    atomicMin(&s_c[REINA_TXLOG_S_FIRST_DAY], lo);
+                    atomicMax(&s_c[REINA_TXLOG_S_LAST_DAY], hi);
+                }
+            }
+            // the interval histograms (LDS)
+            tx_count(s_h, tk && ok ? (int)(REINA_TXLOG_INCUBATION + v * REINA_TXLOG_INCUBATION_BINS) +
+                                         txl_clip((int)oi - (int)ti, REINA_TXLOG_INCUBATION_BINS - 1)
+                                   : -1);
+            tx_count(s_h, both ? (int)(REINA_TXLOG_GENERATION + v * REINA_TXLOG_GENERATION_BINS) +
+                                     txl_clip((int)ti - (int)ts, REINA_TXLOG_GENERATION_BINS - 1)
+                               : -1);
+            tx_count(s_h, ok && osk ? (int)(REINA_TXLOG_SERIAL + v * REINA_TXLOG_SERIAL_BINS) +
+                                          txl_clip((int)oi - (int)os + REINA_TXLOG_SERIAL_SHIFT, REINA_TXLOG_SERIAL_BINS - 1)
+                                    : -1);
+            tx_count(s_h, tk && osk ? (int)(REINA_TXLOG_TOST + v * REINA_TXLOG_TOST_BINS) +
+                                          txl_clip((int)ti - (int)os + REINA_TXLOG_TOST_SHIFT, REINA_TXLOG_TOST_BINS - 1)
+                                    : -1);
+            const uint32_t phase = tk && osk ? (ti < os ? 0u : 1u) : (tk && os == TXL_NONE ? 2u : 3u);
+            tx_count(s_h, linked ? (int)(REINA_TXLOG_LINK_PHASE + v * REINA_TXLOG_PHASES + phase) : -1);
+            // the tables by day (global, aggregated in the wave)
+            const bool in = tk && ti < D;
+            int g = 0;
+            if (in) g = (int)s_grp[age_of(s_as, i, 0, top)];
+            txl_add(inc_t, in ? (int)((ti * REINA_TXLOG_VARIANTS + v) * REINA_TXLOG_MAX_GROUPS) + g : -1, 1ull);
+            txl_add(ons_t, ok && oi < D ? (int)(oi * REINA_TXLOG_VARIANTS + v) : -1, 1ull);
+            const int ck = in ? (int)((ti * REINA_TXLOG_VARIANTS + v) * REINA_TXLOG_COHORT_FIELDS) : -1;
+            txl_add(coh_t, ck, 1ull);
+            txl_add(coh_t + 1, ck, (unsigned long long)n[j]);
+            txl_add(coh_t + 2, ck, RH_STATE(w[j]) >= RS_RECOVERED ? 1ull : 0ull);
+        }
+    }
+    __syncthreads();
+    for (uint32_t k = tid; k < REINA_TXLOG_SCALARS; k += TXL_THREADS)
+        if (s_h[k]) atomicAdd(&R[k], (unsigned long long)s_h[k]);
+    if (tid < REINA_TXLOG_S_NR) {
+        GAS unsigned long long *S = R + REINA_TXLOG_SCALARS;
+        if (tid == REINA_TXLOG_S_FIRST_DAY) {
+            if (s_c[tid] != 0xFFFFFFFFu) atomicMin(&S[tid], (unsigned long long)s_c[tid]);
+        } else if (tid == REINA_TXLOG_S_LAST_DAY) {
+            if (s_c[tid]) atomicMax(&S[tid], (unsigned long long)s_c[tid]);
+        } else if (s_c[tid]) {
+            atomicAdd(&S[tid], (unsigned long long)s_c[tid]);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+
+struct reina_txlog {
+    reina_engine_t *e0 = nullptr;            // the engine, or the group's representative
+    reina_group *g = nullptr;                // a group's log
+    std::vector<reina_engine_t *> members;
+    const MemberRef *d_refs = nullptr;       // the engine's / the group's member table (device)
+    uint32_t *d_log = nullptr;               // [members][stride]
+    size_t stride = 0;                       // words a member: n_agents rounded up to whole tiles
+    bool by_hot = true;                      // k_txlog_day's form (REINA_TXLOG_FORM=log: the log word of every active agent; measurement handle)
+    int64_t last_day = -1;                   // the last day recorded
+};
+
+static void free_txlog(reina_txlog *l) {
+    if (l->d_log) (void)hipFree(l->d_log);
+    delete l;
+}
+
+static uint32_t txlog_grid(const reina_txlog *l, uint32_t units) {
+    const uint32_t K = (uint32_t)l->members.size();
+    uint32_t per = 8u * l->e0->n_cus / K;   // workgroups a member
+    if (per < 1u) per = 1u;
+    return units < per ? (units ? units : 1u) : per;
+}
+
+static int txlog_create(const std::vector<reina_engine_t *> &members, reina_group *g, const MemberRef *d_refs, hipStream_t s, reina_txlog_t **out) {
+    if (!out) return REINA_E_INVALID;
+    for (auto m : members) {
+        if (!m->bound) return REINA_E_NOT_BOUND;
+        if (m->cfg.n_shards > 1 || m->exact || m->coll_fn || m->a2a_fn) {
+            g_last_error = "txlog: sharded engines are refused (links are global ids, and a shard sees only its own agents' onsets), exact attribution included";
+            return REINA_E_INVALID;
+        }
+        if (reinterpret_cast<uintptr_t>(m->buf.hot) & 15u) {
+            g_last_error = "txlog: the hot words must be 16-byte aligned";
+            return REINA_E_INVALID;
+        }
+    }
+    reina_txlog *l = new reina_txlog();
+    l->e0 = members[0];
+    l->g = g;
+    l->members = members;
+    l->d_refs = d_refs;
+    const char *form = std::getenv("REINA_TXLOG_FORM");
+    l->by_hot = !(form && std::strcmp(form, "log") == 0);
+    const uint32_t N = l->e0->cfg.n_agents, K = (uint32_t)members.size();
+    l->stride = ((size_t)N + TXL_TILE - 1u) / TXL_TILE * TXL_TILE;
+    HIP_CHECK_OR(hipMalloc(&l->d_log, sizeof(uint32_t) * l->stride * K), free_txlog(l));
+    const uint32_t grid = txlog_grid(l, ((N + 3u) / 4u + TXL_THREADS - 1u) / TXL_THREADS);
+    if (g)
+        hipLaunchKernelGGL(k_txlog_begin<true>, dim3(grid, K), dim3(TXL_THREADS), 0, s, d_refs, l->e0->h_ref, l->d_log, l->stride, N);
+    else
+        hipLaunchKernelGGL(k_txlog_begin<false>, dim3(grid, 1), dim3(TXL_THREADS), 0, s, d_refs, l->e0->h_ref, l->d_log, l->stride, N);
+    HIP_CHECK_OR(hipGetLastError(), free_txlog(l));
+    *out = l;
+    return REINA_OK;
+}
+
+// behind a day's last launch
+static int txlog_launch_day(reina_txlog *l, uint32_t day, hipStream_t s) {
+    if (day >= REINA_MAX_DAYS) {
+        g_last_error = "txlog: day >= REINA_MAX_DAYS (4096)";
+        return REINA_E_INVALID;
+    }
+    const uint32_t N = l->e0->cfg.n_agents, K = (uint32_t)l->members.size();
+    // (the hot-word tests hold for the days that follow a recorded day: the first day, and a day after a gap, read the log)
+    const uint32_t by_hot = l->by_hot && l->last_day >= 0 && (int64_t)day == l->last_day + 1 ? 1u : 0u;
+    const uint32_t tiles = (N + TXL_TILE - 1u) / TXL_TILE;
+    const uint32_t grid = txlog_grid(l, (tiles + TXL_THREADS / 64u - 1u) / (TXL_THREADS / 64u));
+    if (l->g)
+        hipLaunchKernelGGL(k_txlog_day<true>, dim3(grid, K), dim3(TXL_THREADS), 0, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, N, day, by_hot);
+    else
+        hipLaunchKernelGGL(k_txlog_day<false>, dim3(grid, 1), dim3(TXL_THREADS), 0, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, N, day, by_hot);
+    HIP_CHECK(hipGetLastError());
+    l->last_day = day;
+    return REINA_OK;
+}
+
+static int txlog_report(reina_txlog *l, const uint8_t *age_group, uint32_t n_groups, uint32_t n_days, uint64_t *dev_report, hipStream_t s) {
+    if (!age_group || n_groups < 1u || n_groups > REINA_TXLOG_MAX_GROUPS) {
+        g_last_error = "txlog report: age_group must be a table of groups, 1 <= n_groups <= REINA_TXLOG_MAX_GROUPS";
+        return REINA_E_INVALID;
+    }
+    if (n_days < 1u || n_days > REINA_MAX_DAYS) {
+        g_last_error = "txlog report: n_days must be in [1, REINA_MAX_DAYS]";
+        return REINA_E_INVALID;
+    }
+    if (!dev_report || (reinterpret_cast<uintptr_t>(dev_report) & 15u)) {
+        g_last_error = "txlog report: the report must be a 16-byte aligned device buffer";
+        return REINA_E_INVALID;
+    }
+    const reina_engine_t *e = l->e0;
+    TxlArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.n_agents = e->cfg.n_agents;
+    a.nr_ages = e->cfg.nr_ages;
+    a.n_days = n_days;
+    std::memcpy(a.age_start, e->cfg.age_start, sizeof(a.age_start));
+    for (uint32_t k = 0; k < e->cfg.nr_ages; k++) {
+        if (age_group[k] >= n_groups) {
+            g_last_error = "txlog report: an age's group is not below n_groups";
+            return REINA_E_INVALID;
+        }
+        a.group[k] = age_group[k];
+    }
+    const uint32_t K = (uint32_t)l->members.size();
+    const size_t block = REINA_TXLOG_REPORT_WORDS(n_days) * 8u;
+    HIP_CHECK(hipMemsetAsync(dev_report, 0, block * K, s));
+    HIP_CHECK(hipMemset2DAsync(dev_report + REINA_TXLOG_SCALARS + REINA_TXLOG_S_FIRST_DAY, block, 0xFF, 8u, K, s));
+    const uint32_t tiles = (a.n_agents + TXL_TILE - 1u) / TXL_TILE;
+    uint32_t per = 4u * e->n_cus / K;   // workgroups a member (each flushes its LDS tables once)
+    if (per < 1u) per = 1u;
+    const uint32_t grid = tiles < per ? (tiles ? tiles : 1u) : per;
+    if (l->g)
+        hipLaunchKernelGGL(k_txlog_report<true>, dim3(grid, K), dim3(TXL_THREADS), 0, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, dev_report, a);
+    else
+        hipLaunchKernelGGL(k_txlog_report<false>, dim3(grid, 1), dim3(TXL_THREADS), 0, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, dev_report, a);
+    HIP_CHECK(hipGetLastError());
+    return REINA_OK;
+}
+
+static int txlog_kind(const reina_txlog *l, bool group, const char *what) {
+    if (!l) return REINA_E_INVALID;
+    if ((l->g != nullptr) != group) {
+        g_last_error = std::string(what) + (group ? ": the log was made for one engine -- use the entry point without group_" : ": the log was made for a group -- use the reina_group_txlog_ entry point");
+        return REINA_E_INVALID;
+    }
+    return REINA_OK;
+}
+
+extern "C" {
+
+int reina_txlog_version(void) { return REINA_TXLOG_VERSION; }
+
+int reina_txlog_create(reina_engine_t *e, void *stream, reina_txlog_t **out) {
+    if (!e) return REINA_E_INVALID;
+    if (!e->bound) return REINA_E_NOT_BOUND;
+    return txlog_create(std::vector<reina_engine_t *>(1, e), nullptr, e->d_ref, (hipStream_t)stream, out);
+}
+
+int reina_group_txlog_create(reina_group_t *g, void *stream, reina_txlog_t **out) {
+    if (!g || g->members.empty()) return REINA_E_INVALID;
+    return txlog_create(g->members, g, g->d_refs, (hipStream_t)stream, out);
+}
+
+int reina_txlog_destroy(reina_txlog_t *log) {
+    if (!log) return REINA_E_INVALID;
+    free_txlog(log);
+    return REINA_OK;
+}
+
+int reina_txlog_record_day(reina_txlog_t *log, uint32_t day, void *stream) {
+    if (!log) return REINA_E_INVALID;
+    return txlog_launch_day(log, day, (hipStream_t)stream);
+}
+
+int reina_txlog_run_days(reina_txlog_t *log, const reina_day_t *days, uint32_t n_days, int32_t *history_base, void *stream) {
+    if (!days) return REINA_E_INVALID;
+    if (int rc = txlog_kind(log, false, "reina_txlog_run_days")) return rc;
+    // (always the three-launch day: reina_step_day, never the several-days-in-one-launch form)
+    for (uint32_t k = 0; k < n_days; k++) {
+        reina_day_t d = days[k];
+        d.history_row = history_base ? history_base + (size_t)k * REINA_COUNTER_WORDS : nullptr;
+        if (d.day >= REINA_MAX_DAYS) {
+            g_last_error = "txlog: day >= REINA_MAX_DAYS (4096)";
+            return REINA_E_INVALID;
+        }
+        if (int rc = reina_step_day(log->e0, &d, stream)) return rc;
+        if (int rc = txlog_launch_day(log, d.day, (hipStream_t)stream)) return rc;
+    }
+    return REINA_OK;
+}
+
+int reina_group_txlog_run_days(reina_txlog_t *log, const reina_day_t *days, uint32_t n_days, int32_t *const *history_bases, void *stream) {
+    if (!days) return REINA_E_INVALID;
+    if (int rc = txlog_kind(log, true, "reina_group_txlog_run_days")) return rc;
+    for (uint32_t k = 0; k < n_days; k++)
+        if (days[k].day >= REINA_MAX_DAYS) {
+            g_last_error = "txlog: day >= REINA_MAX_DAYS (4096)";
+            return REINA_E_INVALID;
+        }
+    return group_run_days(log->g, days, n_days, history_bases, stream, nullptr, log);
+}
+
+int reina_txlog_report(reina_txlog_t *log, const uint8_t *age_group, uint32_t n_groups, uint32_t n_days, uint64_t *dev_report, void *stream) {
+    if (int rc = txlog_kind(log, false, "reina_txlog_report")) return rc;
+    return txlog_report(log, age_group, n_groups, n_days, dev_report, (hipStream_t)stream);
+}
+
+int reina_group_txlog_report(reina_txlog_t *log, const uint8_t *age_group, uint32_t n_groups, uint32_t n_days, uint64_t *dev_report, void *stream) {
+    if (int rc = txlog_kind(log, true, "reina_group_txlog_report")) return rc;
+    return txlog_report(log, age_group, n_groups, n_days, dev_report, (hipStream_t)stream);
+}
+
+int reina_txlog_read(reina_txlog_t *log, uint32_t member, uint32_t *out_host, void *stream) {
+    if (!log || !out_host) return REINA_E_INVALID;
+    if (member >= log->members.size()) {
+        g_last_error = "txlog: member out of range";
+        return REINA_E_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_CHECK(hipMemcpyAsync(out_host, log->d_log + (size_t)member * log->stride, sizeof(uint32_t) * log->e0->cfg.n_agents, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return REINA_OK;
+}
+
+int reina_txlog_write(reina_txlog_t *log, uint32_t member, const uint32_t *in_host, void *stream) {
+    if (!log || !in_host) return REINA_E_INVALID;
+    if (member >= log->members.size()) {
+        g_last_error = "txlog: member out of range";
+        return REINA_E_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_CHECK(hipMemcpyAsync(log->d_log + (size_t)member * log->stride, in_host, sizeof(uint32_t) * log->e0->cfg.n_agents, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return REINA_OK;
+}
+
+}  // extern "C"

@@ -1294,9 +1294,11 @@ int reina_group_upload_contact_tables(reina_group_t *g, const reina_contact_tabl
 
 // a policy's launch ahead of a day's opening (k_policy.inc)
 static int policy_launch_day(struct reina_policy *p, const reina_day_t &dp, hipStream_t s);
+// a transmission log's launch behind a day's last one (k_txlog.inc)
+static int txlog_launch_day(struct reina_txlog *l, uint32_t day, hipStream_t s);
 
 static int group_run_days(reina_group_t *g, const reina_day_t *days, uint32_t n_days, int32_t *const *history_bases,
-                          void *stream, struct reina_policy *policy) {
+                          void *stream, struct reina_policy *policy, struct reina_txlog *txlog = nullptr) {
     if (!g || !days) return REINA_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const uint32_t K = (uint32_t)g->members.size();
@@ -1321,6 +1323,7 @@ static int group_run_days(reina_group_t *g, const reina_day_t *days, uint32_t n_
         int rc = policy ? policy_launch_day(policy, dp, s) : REINA_OK;
         if (rc == REINA_OK) rc = launch_day_begin(e0, g->d_refs, K, dp, d, s);
         if (rc == REINA_OK) rc = launch_day_end(e0, g->d_refs, K, dp, s);
+        if (rc == REINA_OK && txlog) rc = txlog_launch_day(txlog, dp.day, s);
         if (rc) {
             e0->h_ref = own_ref;
             return rc;
@@ -1438,3 +1441,6 @@ int reina_profile_read(reina_engine_t *e, double *scan_ms_total, uint64_t *scan_
 
 // triggered interventions (include/reina_policy.h): the deciding kernel and entry points
 #include "k_policy.inc"
+
+// the dated transmission log (include/reina_txlog.h): kernels and entry points
+#include "k_txlog.inc"

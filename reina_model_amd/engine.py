@@ -354,6 +354,9 @@ class Engine:
         # triggered interventions (include/reina_policy.h): likewise
         from .policy import bind_policy_abi
         self.policy_f = bind_policy_abi(lib, prefix)
+        # the dated transmission log (include/reina_txlog.h): likewise
+        from .txlog import bind_txlog_abi
+        self.txlog_f = bind_txlog_abi(lib, prefix)
         self.config = config
         self._h = ctypes.c_void_p()
         self._check(self.f['create'](ctypes.byref(config), ctypes.byref(disease), ctypes.byref(self._h)), 'create')

@@ -24,7 +24,7 @@ from . import simulation
 from .filtering import particle_filter  # noqa: F401  (conditioned ensembles: reina_model_amd/filtering.py)
 
 
-def run_group_plan(contexts, plan, record_history=True, member_plans=None, group=None, policy=None):
+def run_group_plan(contexts, plan, record_history=True, member_plans=None, group=None, policy=None, txlog=False):
     """Execute `plan` (Context.make_plan) for all `contexts` as one engine group.  Returns
     history[len(contexts), days, COUNTER_WORDS] (host) or None.
 
@@ -37,9 +37,20 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
 
     `policy` (policy.Policy; the plan made with it, make_plan(days, policy=...)): every member reacts to its own counters --
     k_policy ahead of every day, one bank of level tables for the whole group.  Every member starts at level 0 with an empty
-    ring; its levels end up in `context.policy_levels`, its mobility factors in `context.mobility_history`."""
+    ring; its levels end up in `context.policy_levels`, its mobility factors in `context.mobility_history`.
+
+    `txlog`: every member keeps a dated transmission log (reina_model_amd/txlog.py), recorded by one launch a day for the
+    whole group; the members' logs end up on `contexts[m].transmission_log` and share the group's device log, which lives as
+    long as they do (and keeps a group made for the run open).  A later call with the same `group` continues them; members that keep logs already are continued
+    whatever `txlog` says.  Not together with a policy."""
     from . import engine as _eng
     from . import policy as _pol
+    from . import txlog as _txl
+    logged = [c.transmission_log is not None for c in contexts]
+    if (txlog or any(logged)) and policy is not None:
+        raise ValueError('run_group_plan: a transmission log and a policy cannot be combined')
+    if any(logged) and not all(logged):
+        raise ValueError('run_group_plan: some members keep a transmission log and some do not')
     if policy is not None:
         if member_plans is not None:
             raise ValueError('run_group_plan: a policy and member_plans (a sweep) cannot be combined')
@@ -53,6 +64,8 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
         if _T is not None:
             _T.append((name, _time.perf_counter()))
     _t('start')
+    if group is None and logged and all(logged) and contexts[0].transmission_log.device is not None:
+        group = contexts[0].transmission_log.device.group   # (a logged group's log keeps its group open)
     own_group = group is None
     if own_group:
         group = _eng.EngineGroup([c.engine for c in contexts])
@@ -60,6 +73,18 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
         raise ValueError('run_group_plan: `group` is not the group of these contexts')
     for c in contexts:
         c._replayed = True
+    glog = None
+    if all(logged) and logged:
+        glog = contexts[0].transmission_log.device
+        if glog is None or glog.group is not group or any(c.transmission_log.device is not glog for c in contexts):
+            raise ValueError("run_group_plan: the members' transmission logs are not those of this group (logs begun one by "
+                             'one, or with another group, cannot be continued as a group)')
+    elif txlog:
+        for c in contexts:
+            _txl.check_capable(c)
+        glog = _txl.DeviceLog(contexts[0].engine, group=group)
+        for m, c in enumerate(contexts):
+            c.transmission_log = _txl.TransmissionLog(c, device=glog, member=m)
     a = group.alloc
     days = plan['days']
     K = len(contexts)
@@ -80,7 +105,7 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
         elif tables is not None:
             group.upload_contact_tables(*tables)
         ptrs = [a.ptr(hist) + row * (m * days + done) for m in range(K)] if record_history else None
-        group.run_day_array(arr, n, ptrs)
+        (glog if glog is not None else group).run_day_array(arr, n, ptrs)
         done += n
     _t('issued')
     if dev is not None:
@@ -109,7 +134,7 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
         for c in contexts:
             c._raise_on_problem(c.engine.read_counters())
     _t('final counters')
-    if own_group:
+    if own_group and glog is None:   # (a group made here for a logged run stays open with its log, and goes with it)
         group.close()
     _t('closed')
     if _T is not None:
@@ -314,3 +339,17 @@ def transmission_reports(contexts, age_groups=None, group=None):
     for r in reps:
         r.group_labels = labels
     return reps
+
+
+def log_reports(contexts, age_groups=None, n_days=None):
+    """txlog.LogReport of every context, between the same two days.  The members of a logged group (run_group_plan(...,
+    txlog=True)) are reported by ONE launch (reina_group_txlog_report); contexts that keep logs of their own one by one."""
+    from . import txlog as _txl
+    contexts = list(contexts)
+    if any(c.transmission_log is None for c in contexts):
+        raise ValueError('log_reports: a context keeps no transmission log')
+    glog = contexts[0].transmission_log.device
+    if glog is not None and glog.group is not None and all(c.transmission_log.device is glog for c in contexts) \
+            and [c.transmission_log.member for c in contexts] == list(range(glog.members)):
+        return _txl.report_group(glog, contexts, age_groups, n_days)
+    return [c.transmission_log.report(age_groups, n_days) for c in contexts]

@@ -99,6 +99,13 @@ def check_pairs(pairs, K):
     return p
 
 
+def _check_no_logs(contexts):
+    """a clone overwrites a member's state but not its dated transmission log (reina_model_amd/txlog.py)"""
+    if any(getattr(c, 'transmission_log', None) is not None for c in contexts):
+        raise ValueError('particle filter: members that keep a transmission log are refused (a clone overwrites a '
+                         "member's state but not its log)")
+
+
 def clone_group(group, pairs):
     """Member dst of the engine group gets member src's carried state, for every (dst, src) in `pairs`: ONE launch on the
     device (reina_group_clone), clone_state per pair for host-memory engines."""
@@ -303,6 +310,7 @@ class FilterResult:
     def __init__(self, planner, contexts, group, start_day, start_date, filter_seed):
         self.planner = planner
         self.contexts = contexts
+        _check_no_logs(contexts)
         self.group = group
         self.start_day = start_day
         self.start_date = _as_date(start_date)
@@ -383,6 +391,7 @@ class FilterResult:
         from . import ensemble
         if self.group is None:
             raise ValueError('forecast: the filter has been closed')
+        _check_no_logs(self.contexts)
         d0 = self.start_day + self.days
         plan = self.planner.make_plan(int(days))
         hist = ensemble.run_group_plan(self.contexts, plan, group=self.group)

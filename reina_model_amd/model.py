@@ -227,16 +227,18 @@ class Context:
     """MI355X-native agent engine with the reference `Context` protocol (main.pyx:1746-2101)."""
 
     def __init__(self, population_params, healthcare_params, disease_params, start_date,
-                 random_seed=4321, device='cuda:0', engine_factory=None, comm=None, strict=False, policy=None):
+                 random_seed=4321, device='cuda:0', engine_factory=None, comm=None, strict=False, policy=None, txlog=False):
         """`comm` (sharding.TorchComm or compatible: .rank, .world, .all_reduce_sum/max) makes this
         Context one shard of a population split over comm.world engine instances; population,
         beds, ICU units and import / vaccination quotas given here are the GLOBAL ones.
-        `policy` (policy.Policy): run() and run_plan() take the policy route (reina_model_amd/policy.py)."""
+        `policy` (policy.Policy): run() and run_plan() take the policy route (reina_model_amd/policy.py).
+        `txlog`: keep a dated transmission log from the start (reina_model_amd/txlog.py; start_transmission_log())."""
         from .sharding import split_count, split_population
         self.comm = comm
         self.strict = bool(strict)   # iterate() raises on the day of a problem (main.pyx:2017-2018)
         self.policy = policy
         self.policy_levels = None    # after a policy run: the level in force on each of its days
+        self.transmission_log = None  # txlog.TransmissionLog once begun: run(), run_plan() and iterate() record every day
         if policy is not None and comm is not None and (comm.world > 1 or getattr(comm, 'always_collective', False)):
             raise ValueError('policy: sharded Contexts are refused (the signal would need the all-reduce of the shards)')
         # testing aid: take the begin / all-reduce / end path even with a single shard
@@ -393,6 +395,28 @@ class Context:
         # main.pyx:1780-1781: the initial condition is applied last, before any intervention exists
         if ipc is not None and ipc.has_initial_state():
             self._set_initial_state(ipc)
+        if txlog:
+            self.start_transmission_log()
+
+    def start_transmission_log(self):
+        """Begin a dated transmission log (txlog.TransmissionLog, also ctx.transmission_log): from now on run(), run_plan()
+        and iterate() record every agent's day of infection and of symptom onset.  Whoever is infected already gets the code
+        BEFORE: a fresh Context starts with nothing but its initial condition marked, a Context that has run (or was restored
+        from a snapshot) with its past.  On the GPU the log lives in device memory and costs one short launch a day; an engine
+        library without the log's entry points keeps it on the host (txlog.run_host_driven)."""
+        from . import txlog as _txl
+        if self.transmission_log is not None:
+            raise ValueError('start_transmission_log: this Context keeps a log already')
+        self.transmission_log = _txl.TransmissionLog(self)
+        return self.transmission_log
+
+    def _run_day_array(self, arr, n, history_ptr):
+        """engine.run_day_array, or the logged entry point when a log is attached"""
+        log = self.transmission_log
+        if log is None:
+            self.engine.run_day_array(arr, n, history_ptr)
+        else:
+            log.device.run_day_array(arr, n, history_ptr)
 
     def _set_initial_state(self, ipc):
         """Population.set_initial_state (main.pyx:1452-1516) on the engine; a sharded population
@@ -602,6 +626,8 @@ class Context:
     def _step(self, d):
         if self._in_stream or (self.n_shards == 1 and not self.always_collective):
             self.engine.step_day(d)
+            if self.transmission_log is not None:
+                self.transmission_log.record_day(d.day)
         else:
             # the day phase by phase, the collectives each phase asks for in between: one all-reduce (the cross-shard
             # pressure block with the bed / ICU event maps), and under exact attribution the record exchanges
@@ -671,6 +697,8 @@ class Context:
             from . import policy as _pol
             self._replayed = True
             return _pol.run_plan_device(self, plan, record_history)
+        if self.transmission_log is not None and not self.transmission_log.on_device:
+            raise ValueError('run_plan: this Context keeps its log on the host (txlog.run_host_driven runs its days)')
         days = plan['days']
         a = self.engine.alloc
         self._replayed = True
@@ -681,7 +709,7 @@ class Context:
             if tables is not None:
                 self.engine.upload_contact_tables(*tables)
             ptr = base + 4 * _eng.COUNTER_WORDS * done if record_history else None
-            self.engine.run_day_array(arr, n, ptr)
+            self._run_day_array(arr, n, ptr)
             done += n
         self.mobility_history = plan['mobility_history']
         self.day = plan['start_day'] + days
@@ -719,7 +747,7 @@ class Context:
             nonlocal pending, issued, chunk
             if pending:
                 arr = (_eng.Day * len(pending))(*pending)
-                self.engine.run_day_array(arr, len(pending), base + row * issued if record_history else None)
+                self._run_day_array(arr, len(pending), base + row * issued if record_history else None)
                 issued += len(pending)
                 pending = []
                 chunk = min(chunk * 2, 64)
@@ -757,6 +785,9 @@ class Context:
             if self.engine.policy_f is None:
                 return _pol.run_host_driven(self, self.policy, days, record_history)
             return _pol.run_device(self, days, record_history)
+        if self.transmission_log is not None and not self.transmission_log.on_device:
+            from . import txlog as _txl
+            return _txl.run_host_driven(self, days, record_history)
         if self._in_stream or (self.n_shards == 1 and not self.always_collective):
             return self._run_streamed(days, record_history)
         a = self.engine.alloc
@@ -877,6 +908,8 @@ class Context:
         from . import snapshot as _snap
         if self.policy is not None:
             raise ValueError('snapshot: a Context with a policy is refused (the policy state lives outside the engine state)')
+        if self.transmission_log is not None:
+            raise ValueError('snapshot: a Context with a transmission log is refused (the log lives outside the engine state)')
         self._check_snapshot_capable('snapshot')
         counters = self._read_counters_global()
         if int(counters[_eng.C_NR * _eng.MAX_AGES + _eng.S_PROBLEM]) != 0:
@@ -941,6 +974,8 @@ class Context:
         from . import snapshot as _snap
         st = snap.state
         self._check_snapshot_capable('restore')
+        if self.transmission_log is not None:
+            raise ValueError('restore: this Context keeps a transmission log already (begin it after the restore: start_transmission_log)')
         if self.day != 0 or self._stepped:
             raise ValueError('restore: only into a freshly made Context (this one has stepped)')
         if st.get('format') != _snap.HOST_STATE_FORMAT:

@@ -1,0 +1,519 @@
+"""A dated transmission log: the day of infection and the day of symptom onset of every agent (include/reina_txlog.h;
+DESIGN.md section 6f).
+
+The engine knows who infected whom (transmission.py) but keeps no dates.  A LOG is one uint32 per agent, owned by the log
+object, outside the engine state:
+
+    word = onset_day << 16 | infection_day        codes: NONE 0xFFFF (not yet / never), BEFORE 0xFFFE (before the log began)
+
+Days are absolute day numbers (Context.day, < 4096).  A day is KNOWN when it is neither code.
+
+  begin        every agent with state != 0 gets infection BEFORE; of those, the ones in state >= ILLNESS get onset BEFORE too;
+               every other half word is NONE.
+  record day d with w the agent's hot word after day d:  infection == NONE and state(w) != 0 -> infection = d;
+               onset == NONE and state(w) >= ILLNESS -> onset = d.  Nothing is ever overwritten.
+  report       between two days: the epidemic curve by date of infection, the onsets by date, the cohorts behind the case
+               reproduction number, and the incubation / generation / serial / onset-to-transmission intervals of every link,
+               as exact integer counts (LogReport).
+
+`begin_numpy`, `record_numpy` and `report_numpy` are the executable specification: the library's kernels (k_txlog_begin,
+k_txlog_day, k_txlog_report) compute the same words.  `run_host_driven` is the plain formulation -- iterate() and
+record_numpy a day at a time, on any engine -- that the device path is tested against, and what a Context on an engine
+library without the log's entry points takes.
+
+In line lists, -1 stands for NONE and -2 for BEFORE.
+"""
+import ctypes
+
+import numpy as np
+
+from . import engine as _eng
+
+TXLOG_VERSION = 1              # include/reina_txlog.h: REINA_TXLOG_VERSION
+NONE, BEFORE = 0xFFFF, 0xFFFE
+VARIANTS, MAX_GROUPS = 4, 16
+INCUBATION_BINS, GENERATION_BINS, SERIAL_BINS, TOST_BINS, PHASES, COHORT_FIELDS = 64, 64, 128, 64, 4, 3
+SERIAL_SHIFT, TOST_SHIFT = 32, 24
+INCUBATION = 0
+GENERATION = INCUBATION + VARIANTS * INCUBATION_BINS
+SERIAL = GENERATION + VARIANTS * GENERATION_BINS
+TOST = SERIAL + VARIANTS * SERIAL_BINS
+LINK_PHASE = TOST + VARIANTS * TOST_BINS
+SCALARS = LINK_PHASE + VARIANTS * PHASES
+SCALAR_NAMES = ('infected', 'dated', 'before', 'with_onset', 'links', 'links_dated', 'generation_nonpositive', 'first_day',
+                'last_day', 'out_of_range', 'bad_links')
+S_NR = 16
+FIXED_WORDS = SCALARS + S_NR
+DAY_WORDS = VARIANTS * (MAX_GROUPS + 1 + COHORT_FIELDS)
+PHASE_NAMES = ('presymptomatic', 'symptomatic', 'infector_without_onset', 'undated')
+S_ILLNESS, S_RECOVERED = 2, 5   # csrc/reina_prims.h: RS_ILLNESS, RS_RECOVERED
+
+TXLOG_FUNCTIONS = ('txlog_version', 'txlog_create', 'group_txlog_create', 'txlog_destroy', 'txlog_record_day', 'txlog_run_days',
+                   'group_txlog_run_days', 'txlog_report', 'group_txlog_report', 'txlog_read', 'txlog_write')
+
+
+def incidence_offset(n_days):
+    return FIXED_WORDS
+
+
+def onsets_offset(n_days):
+    return incidence_offset(n_days) + int(n_days) * VARIANTS * MAX_GROUPS
+
+
+def cohort_offset(n_days):
+    return onsets_offset(n_days) + int(n_days) * VARIANTS
+
+
+def report_words(n_days):
+    """include/reina_txlog.h: REINA_TXLOG_REPORT_WORDS"""
+    return FIXED_WORDS + int(n_days) * DAY_WORDS
+
+
+def bind_txlog_abi(lib, prefix):
+    """The log's entry points of a library, or None when it has none."""
+    if not all(hasattr(lib, prefix + n) for n in TXLOG_FUNCTIONS):
+        return None
+    f = {n: getattr(lib, prefix + n) for n in TXLOG_FUNCTIONS}
+    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
+    f['txlog_version'].argtypes = []
+    f['txlog_create'].argtypes = [vp, vp, vp]
+    f['group_txlog_create'].argtypes = [vp, vp, vp]
+    f['txlog_destroy'].argtypes = [vp]
+    f['txlog_record_day'].argtypes = [vp, u32, vp]
+    f['txlog_run_days'].argtypes = [vp, vp, u32, vp, vp]
+    f['group_txlog_run_days'].argtypes = [vp, vp, u32, vp, vp]
+    f['txlog_report'].argtypes = [vp, vp, u32, u32, vp, vp]
+    f['group_txlog_report'].argtypes = [vp, vp, u32, u32, vp, vp]
+    f['txlog_read'].argtypes = [vp, u32, vp, vp]
+    f['txlog_write'].argtypes = [vp, u32, vp, vp]
+    for n in TXLOG_FUNCTIONS:
+        f[n].restype = ctypes.c_int
+    if f['txlog_version']() != TXLOG_VERSION:
+        raise _eng.EngineError('%stxlog_version() = %d, this binding is written for %d' % (prefix, f['txlog_version'](), TXLOG_VERSION))
+    return f
+
+
+# ------------------------------------------------------------------------------------------------ the specification
+
+def begin_numpy(hot):
+    """the log of a state as the begin pass leaves it"""
+    st = np.asarray(hot).view(np.uint32).ravel() & 7
+    inf = np.where(st != 0, BEFORE, NONE).astype(np.uint32)
+    ons = np.where(st >= S_ILLNESS, BEFORE, NONE).astype(np.uint32)
+    return ons << 16 | inf
+
+
+def record_numpy(log, hot, day):
+    """`log` after day `day` has been recorded from the hot words as they stand after that day (a new array)"""
+    day = int(day)
+    if not 0 <= day < _eng.MAX_DAYS:
+        raise ValueError('day %d: the log holds days below %d' % (day, _eng.MAX_DAYS))
+    log = np.asarray(log, dtype=np.uint32).ravel()
+    st = np.asarray(hot).view(np.uint32).ravel() & 7
+    inf, ons = log & 0xFFFF, log >> 16
+    inf = np.where((inf == NONE) & (st != 0), day, inf).astype(np.uint32)
+    ons = np.where((ons == NONE) & (st >= S_ILLNESS), day, ons).astype(np.uint32)
+    return ons << 16 | inf
+
+
+def _group_table(age_group, nr_ages):
+    from .transmission import _group_table as g
+    return g(age_group, nr_ages)
+
+
+def report_numpy(hot, infector, n_infected, log, age_start, age_group, n_days):
+    """The report of one state and its log (the specification of reina_txlog_report).  hot: uint32[N]; infector, n_infected:
+    int32[N] (the cold record's fields); log: uint32[N]; age_start: first agent of each age ([A] = N, padded with N);
+    age_group: group of each age (< MAX_GROUPS); n_days: the dated tables hold the days [0, n_days)."""
+    hot = np.asarray(hot).view(np.uint32).ravel()
+    n = len(hot)
+    n_days = int(n_days)
+    if not 1 <= n_days <= _eng.MAX_DAYS:
+        raise ValueError('n_days must be in [1, %d]' % _eng.MAX_DAYS)
+    src = np.asarray(infector).view(np.int32).ravel().astype(np.int64)
+    cnt = np.asarray(n_infected).view(np.uint32).ravel().astype(np.uint64)
+    log = np.asarray(log, dtype=np.uint32).ravel()
+    age_start = np.asarray(age_start, dtype=np.int64).ravel()
+    nr_ages = min(len(np.asarray(age_group).ravel()), _eng.MAX_AGES, len(age_start) - 1)
+    table, n_groups = _group_table(age_group, nr_ages)
+    words = np.zeros(report_words(n_days), dtype=np.uint64)
+    state = hot & 7
+    idx = np.flatnonzero(state != 0)
+    w = hot[idx]
+    v = ((w >> 8) & 3).astype(np.int64)
+    t = (log[idx] & 0xFFFF).astype(np.int64)
+    o = (log[idx] >> 16).astype(np.int64)
+    tk, ok = t < BEFORE, o < BEFORE
+
+    def hist(offset, bins, sel, value):
+        cell = v[sel] * bins + np.clip(value, 0, bins - 1)
+        words[offset:offset + VARIANTS * bins] = np.bincount(cell, minlength=VARIANTS * bins).astype(np.uint64)
+
+    hist(INCUBATION, INCUBATION_BINS, tk & ok, (o - t)[tk & ok])
+    s = src[idx]
+    root = s == -1
+    in_range = (s >= 0) & (s < n) & (s != idx)
+    linked = np.zeros(len(idx), dtype=bool)
+    linked[in_range] = state[s[in_range]] != 0
+    bad = ~root & ~linked
+    sl = np.zeros(len(idx), dtype=np.uint32)
+    sl[linked] = log[s[linked]]
+    ts, os_ = (sl & 0xFFFF).astype(np.int64), (sl >> 16).astype(np.int64)
+    tsk, osk = linked & (ts < BEFORE), linked & (os_ < BEFORE)
+    both = tk & tsk
+    hist(GENERATION, GENERATION_BINS, both, (t - ts)[both])
+    hist(SERIAL, SERIAL_BINS, ok & osk, (o - os_ + SERIAL_SHIFT)[ok & osk])
+    hist(TOST, TOST_BINS, tk & osk, (t - os_ + TOST_SHIFT)[tk & osk])
+    phase = np.where(tk & osk, np.where(t < os_, 0, 1), np.where(tk & (os_ == NONE), 2, 3))
+    hist(LINK_PHASE, PHASES, linked, phase[linked])
+
+    ages = np.clip(np.searchsorted(age_start[:nr_ages + 1], idx, side='right') - 1, 0, nr_ages - 1)
+    g = table[ages].astype(np.int64)
+    inr = tk & (t < n_days)
+    a, b, c = incidence_offset(n_days), onsets_offset(n_days), cohort_offset(n_days)
+    words[a:b] = np.bincount((t[inr] * VARIANTS + v[inr]) * MAX_GROUPS + g[inr], minlength=b - a).astype(np.uint64)
+    onr = ok & (o < n_days)
+    words[b:c] = np.bincount(o[onr] * VARIANTS + v[onr], minlength=c - b).astype(np.uint64)
+    key = t[inr] * VARIANTS + v[inr]
+    coh = np.zeros((n_days * VARIANTS, COHORT_FIELDS), dtype=np.uint64)
+    coh[:, 0] = np.bincount(key, minlength=len(coh)).astype(np.uint64)
+    np.add.at(coh[:, 1], key, cnt[idx][inr])
+    coh[:, 2] = np.bincount(key[(w[inr] & 7) >= S_RECOVERED], minlength=len(coh)).astype(np.uint64)
+    words[c:] = coh.ravel()
+    sc = dict(infected=len(idx), dated=int(tk.sum()), before=int((t == BEFORE).sum()), with_onset=int(ok.sum()),
+              links=int(linked.sum()), links_dated=int(both.sum()), generation_nonpositive=int((both & (t <= ts)).sum()),
+              first_day=int(t[tk].min()) if tk.any() else (1 << 64) - 1, last_day=int(t[tk].max()) if tk.any() else 0,
+              out_of_range=int((tk & (t >= n_days)).sum()) + int((ok & (o >= n_days)).sum()), bad_links=int(bad.sum()))
+    for k, name in enumerate(SCALAR_NAMES):
+        words[SCALARS + k] = sc[name]
+    return LogReport(words, n_days, n_groups)
+
+
+# ------------------------------------------------------------------------------------------------ reports
+
+class _Intervals:
+    """one interval distribution: counts by value (a pandas Series through .series()), and its mean"""
+
+    def __init__(self, counts, shift, name):
+        self.counts = np.asarray(counts, dtype=np.int64)
+        self.values = np.arange(len(self.counts)) - shift
+        self.name = name
+
+    def series(self):
+        import pandas as pd
+        return pd.Series(self.counts, index=pd.Index(self.values, name=self.name), name='count')
+
+    def total(self):
+        return int(self.counts.sum())
+
+    def mean(self):
+        """None when empty; the end bins hold the clipped values"""
+        n = self.total()
+        return float((self.counts * self.values).sum()) / n if n else None
+
+    def quantile(self, q):
+        n = self.total()
+        if not n:
+            return None
+        return int(self.values[np.searchsorted(np.cumsum(self.counts), q * n, side='left')])
+
+
+class LogReport:
+    """One report: the words of include/reina_txlog.h as named arrays, plus what is derived from them."""
+
+    def __init__(self, words, n_days, n_groups=MAX_GROUPS, group_labels=None, start_date=None):
+        w = np.asarray(words, dtype=np.uint64).ravel()
+        n_days = int(n_days)
+        if len(w) != report_words(n_days):
+            raise ValueError('a log report of %d days has %d words' % (n_days, report_words(n_days)))
+        self.words, self.n_days, self.n_groups = w, n_days, int(n_groups)
+        self.group_labels = list(group_labels) if group_labels is not None else None
+        self.start_date = start_date
+        self.incubation = w[INCUBATION:GENERATION].reshape(VARIANTS, INCUBATION_BINS)
+        self.generation = w[GENERATION:SERIAL].reshape(VARIANTS, GENERATION_BINS)
+        self.serial = w[SERIAL:TOST].reshape(VARIANTS, SERIAL_BINS)
+        self.tost = w[TOST:LINK_PHASE].reshape(VARIANTS, TOST_BINS)
+        self.link_phase = w[LINK_PHASE:SCALARS].reshape(VARIANTS, PHASES)
+        a, b, c = incidence_offset(n_days), onsets_offset(n_days), cohort_offset(n_days)
+        self.incidence = w[a:b].reshape(n_days, VARIANTS, MAX_GROUPS)
+        self.onsets = w[b:c].reshape(n_days, VARIANTS)
+        self.cohort = w[c:].reshape(n_days, VARIANTS, COHORT_FIELDS)
+        for k, name in enumerate(SCALAR_NAMES):
+            setattr(self, name, int(w[SCALARS + k]))
+        if self.dated == 0:
+            self.first_day = self.last_day = -1
+
+    def __eq__(self, other):
+        return isinstance(other, LogReport) and self.n_days == other.n_days and np.array_equal(self.words, other.words)
+
+    def __repr__(self):
+        return 'LogReport(days=%d, infected=%d, dated=%d, before=%d, links=%d)' % (self.n_days, self.infected, self.dated, self.before, self.links)
+
+    def _dates(self):
+        import pandas as pd
+        if self.start_date is None:
+            return pd.RangeIndex(self.n_days, name='day')
+        return pd.date_range(str(self.start_date), periods=self.n_days, name='date')
+
+    def _v(self, arr, variant):
+        """one variant's part of an array ([variant, ...] or [day, variant, ...]), or the sum over the variants"""
+        axis = 0 if arr.ndim == 2 else 1
+        if variant is None:
+            return arr.sum(axis=axis, dtype=np.uint64)
+        return np.take(arr, int(variant), axis=axis)
+
+    def incidence_frame(self, variant=None):
+        """infections by date of infection (rows) and age group (columns), of one variant or all"""
+        import pandas as pd
+        m = self._v(self.incidence, variant)[:, :self.n_groups].astype(np.int64)
+        labels = self.group_labels or [str(k) for k in range(self.n_groups)]
+        return pd.DataFrame(m, index=self._dates(), columns=pd.Index(labels, name='age_group'))
+
+    def onset_series(self, variant=None):
+        import pandas as pd
+        o = self.onsets.sum(axis=1, dtype=np.uint64) if variant is None else self.onsets[:, int(variant)]   # ([day, variant])
+        return pd.Series(o.astype(np.int64), index=self._dates(), name='onsets')
+
+    def incubation_period(self, variant=None):
+        return _Intervals(self._v(self.incubation, variant), 0, 'incubation_period')
+
+    def generation_interval(self, variant=None):
+        return _Intervals(self._v(self.generation, variant), 0, 'generation_interval')
+
+    def serial_interval(self, variant=None):
+        return _Intervals(self._v(self.serial, variant), SERIAL_SHIFT, 'serial_interval')
+
+    def onset_to_transmission(self, variant=None):
+        return _Intervals(self._v(self.tost, variant), TOST_SHIFT, 'onset_to_transmission')
+
+    def presymptomatic_share(self, variant=None):
+        """links whose infectee was infected before the infector's onset, over the links where both days are known; None
+        when there is none"""
+        p = self._v(self.link_phase, variant)
+        n = int(p[0]) + int(p[1])
+        return int(p[0]) / n if n else None
+
+    def case_reproduction_number(self, variant=None):
+        """by date of infection: R_c (mean offspring of the agents infected that day so far; NaN for an empty cohort), the
+        cohort's size and the share of it that is removed (R_c of an open cohort is censored)"""
+        import pandas as pd
+        c = self._v(self.cohort, variant).astype(np.float64)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            rc, closed = c[:, 1] / c[:, 0], c[:, 2] / c[:, 0]
+        return pd.DataFrame(dict(r_c=rc, cohort=c[:, 0].astype(np.int64), closed_share=closed), index=self._dates())
+
+
+# ------------------------------------------------------------------------------------------------ logs
+
+def _is_device(engine):
+    return getattr(engine.alloc, 'torch', None) is not None
+
+
+def check_capable(ctx):
+    if ctx.n_shards != 1 or ctx.always_collective:
+        raise ValueError('transmission log: sharded Contexts are refused (links are global ids, and a shard sees only its own '
+                         "agents' onsets)")
+    if ctx.policy is not None:
+        raise ValueError('transmission log: a Context with a policy is refused (the policy route runs its own days)')
+
+
+def _host_array(t):
+    return np.array(t.cpu().numpy() if hasattr(t, 'cpu') else t)
+
+
+class DeviceLog:
+    """The library's log of one engine, or of the members of an engine group (include/reina_txlog.h)."""
+
+    def __init__(self, engine, group=None):
+        f = engine.txlog_f
+        if f is None:
+            raise _eng.EngineError('the engine library has no transmission-log entry points (include/reina_txlog.h)')
+        self.f, self.engine, self.group = f, engine, group
+        self.members = 1 if group is None else len(group.engines)
+        self._h = ctypes.c_void_p()
+        if group is None:
+            engine._check(f['txlog_create'](engine._h, engine.alloc.stream(), ctypes.byref(self._h)), 'txlog_create')
+        else:
+            engine._check(f['group_txlog_create'](group._h, engine.alloc.stream(), ctypes.byref(self._h)), 'group_txlog_create')
+
+    def close(self):
+        if self._h:
+            self.f['txlog_destroy'](self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _touch(self):
+        for e in ([self.engine] if self.group is None else self.group.engines):
+            e._prefetched = False
+
+    def record_day(self, day):
+        self.engine._check(self.f['txlog_record_day'](self._h, int(day), self.engine.alloc.stream()), 'txlog_record_day')
+
+    def run_day_array(self, arr, n, history):
+        """Engine.run_day_array / EngineGroup.run_day_array with the record launch behind every day"""
+        self._touch()
+        if self.group is None:
+            self.engine._check(self.f['txlog_run_days'](self._h, arr, n, history, self.engine.alloc.stream()), 'txlog_run_days')
+            return
+        hp = None
+        if history is not None:
+            hp = (ctypes.c_void_p * self.members)(*[int(p) for p in history])
+        self.engine._check(self.f['group_txlog_run_days'](self._h, arr, n, hp, self.engine.alloc.stream()), 'group_txlog_run_days')
+
+    def words(self, member=0):
+        out = np.zeros(self.engine.config.n_agents, dtype=np.uint32)
+        self.engine._check(self.f['txlog_read'](self._h, int(member), out.ctypes.data, self.engine.alloc.stream()), 'txlog_read')
+        return out
+
+    def set_words(self, words, member=0):
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        if len(w) != self.engine.config.n_agents:
+            raise ValueError('a log has one word per agent')
+        self.engine._check(self.f['txlog_write'](self._h, int(member), w.ctypes.data, self.engine.alloc.stream()), 'txlog_write')
+
+    def report_words(self, table, n_groups, n_days):
+        """[members, report_words(n_days)] uint64: one launch for all members"""
+        torch = self.engine.alloc.torch
+        rep = torch.empty(self.members * report_words(n_days), dtype=torch.int64, device=self.engine.alloc.device)
+        name = 'txlog_report' if self.group is None else 'group_txlog_report'
+        self.engine._check(self.f[name](self._h, table.ctypes.data, int(n_groups), int(n_days), rep.data_ptr(), self.engine.alloc.stream()), name)
+        self._touch()
+        return rep.cpu().numpy().view(np.uint64).reshape(self.members, report_words(n_days))
+
+
+class TransmissionLog:
+    """The log of one Context (ctx.transmission_log): on the device when the engine library has the log's entry points, in
+    host memory otherwise (or with host=True: the plain formulation).  A member of a logged engine group shares the group's
+    DeviceLog (`device`, `member`)."""
+
+    def __init__(self, ctx, host=False, device=None, member=0):
+        check_capable(ctx)
+        self.ctx, self.member = ctx, int(member)
+        self.begin_day = int(ctx.day)
+        self.device, self._words = device, None
+        if device is None:
+            if not host and _is_device(ctx.engine) and ctx.engine.txlog_f is not None:
+                self.device = DeviceLog(ctx.engine)
+            else:
+                self._words = begin_numpy(_host_array(ctx.engine.tensors['hot']))
+
+    @property
+    def on_device(self):
+        return self.device is not None
+
+    def close(self):
+        if self.device is not None and self.device.group is None:
+            self.device.close()
+
+    def record_day(self, day):
+        """behind a day the caller stepped itself (Context.iterate does)"""
+        if self.device is not None:
+            self.device.record_day(day)
+        else:
+            self._words = record_numpy(self._words, _host_array(self.ctx.engine.tensors['hot']), day)
+
+    def words(self):
+        """uint32[n_agents], a host copy"""
+        return self.device.words(self.member) if self.device is not None else self._words.copy()
+
+    def set_words(self, words):
+        """replace the words (a log saved by words(), continued on the same state)"""
+        if self.device is not None:
+            self.device.set_words(words, self.member)
+        else:
+            self._words = np.array(words, dtype=np.uint32)
+
+    def infection_day(self):
+        """int64[n_agents]: the day of infection, -1 NONE, -2 BEFORE"""
+        return _signed(self.words() & 0xFFFF)
+
+    def onset_day(self):
+        return _signed(self.words() >> 16)
+
+    def report(self, age_groups=None, n_days=None):
+        """LogReport of the days [0, n_days) (default: the days run so far)"""
+        ctx = self.ctx
+        table, labels = ctx._tx_groups(age_groups)
+        n_days = max(int(ctx.day), 1) if n_days is None else int(n_days)
+        if not 1 <= n_days <= _eng.MAX_DAYS:
+            raise ValueError('n_days must be in [1, %d]' % _eng.MAX_DAYS)
+        if self.device is not None and self.device.group is None:
+            t8, ng = _group_table(table, ctx.nr_ages)
+            w = self.device.report_words(t8, max(ng, len(labels)), n_days)[0]
+        else:
+            e = ctx.engine
+            n = e.config.n_agents
+            cold = _host_array(e.tensors['cold']).view(np.uint32).reshape(n, _eng.COLD_WORDS)
+            w = report_numpy(_host_array(e.tensors['hot']), cold[:, 2], cold[:, 3], self.words(), ctx.age_start, table, n_days).words
+        return LogReport(w, n_days, len(labels), labels, ctx.start_date)
+
+    def line_list(self):
+        """One row per infected agent (a pandas DataFrame, built on the host from the hot words, the cold records and the log):
+        agent, age, infector (-1: an import or the initial condition), infector_age (-1 without one), infection_day and
+        onset_day (-1 NONE, -2 BEFORE), variant, severity, state, detected, n_infected."""
+        import pandas as pd
+        e = self.ctx.engine
+        n = e.config.n_agents
+        hot = _host_array(e.tensors['hot']).view(np.uint32)
+        cold = _host_array(e.tensors['cold']).view(np.int32).reshape(n, _eng.COLD_WORDS)
+        log = self.words()
+        idx = np.flatnonzero(hot & 7)
+        starts = np.asarray(self.ctx.age_start[:self.ctx.nr_ages + 1])
+        age = lambda i: np.clip(np.searchsorted(starts, i, side='right') - 1, 0, self.ctx.nr_ages - 1)
+        src = cold[idx, 2].astype(np.int64)
+        has = (src >= 0) & (src < n)
+        w = hot[idx]
+        return pd.DataFrame(dict(
+            agent=idx, age=age(idx), infector=np.where(has, src, -1), infector_age=np.where(has, age(np.where(has, src, 0)), -1),
+            infection_day=_signed(log[idx] & 0xFFFF), onset_day=_signed(log[idx] >> 16), variant=((w >> 8) & 3).astype(np.int64),
+            severity=np.minimum((w >> 3) & 7, 4).astype(np.int64), state=(w & 7).astype(np.int64), detected=(w & 0x40) != 0,
+            n_infected=cold[idx, 3].astype(np.int64)))
+
+
+def _signed(half):
+    h = np.asarray(half).astype(np.int64)
+    return np.where(h == NONE, -1, np.where(h == BEFORE, -2, h))
+
+
+def run_host_driven(ctx, days, record_history=True, on_day=None):
+    """`days` days with the log kept the plain way: per day iterate(), read the hot words back, record_numpy -- one blocking
+    round trip a day, on any engine.  Begins a host-side log (ctx.transmission_log) when the Context has none.  Returns history
+    like Context.run.  on_day(day, hot, log_before, log_after), when given, is called after every day (the tests' handle)."""
+    log = ctx.transmission_log
+    if log is None:
+        log = ctx.transmission_log = TransmissionLog(ctx, host=True)
+    if log.on_device:
+        raise ValueError('run_host_driven: this Context keeps its log on the device')
+    rows = []
+    ctx.mobility_history = []
+    for _ in range(days):
+        if record_history:
+            rows.append(ctx.engine.read_counters())
+        ctx.mobility_history.append(float(ctx.contact_matrix.mobility_factor))
+        d, changed = ctx._build_day(None)
+        if changed:
+            ctx._upload_tables()
+        ctx.engine.step_day(d)
+        ctx.day += 1
+        hot = _host_array(ctx.engine.tensors['hot']).view(np.uint32)
+        before = log._words
+        log._words = record_numpy(before, hot, d.day)
+        if on_day is not None:
+            on_day(int(d.day), hot, before, log._words)
+    ctx._raise_on_problem(ctx.engine.read_counters())
+    return np.stack(rows) if record_history and rows else (np.zeros((0, _eng.COUNTER_WORDS), dtype=np.int32) if record_history else None)
+
+
+def report_group(device_log, contexts, age_groups=None, n_days=None):
+    """The reports of every member of a logged group: one launch for all members."""
+    c0 = contexts[0]
+    table, labels = c0._tx_groups(age_groups)
+    n_days = max(int(c0.day), 1) if n_days is None else int(n_days)
+    t8, ng = _group_table(table, c0.nr_ages)
+    w = device_log.report_words(t8, max(ng, len(labels)), n_days)
+    return [LogReport(w[m].copy(), n_days, len(labels), labels, c.start_date) for m, c in enumerate(contexts)]
