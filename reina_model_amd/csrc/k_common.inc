@@ -197,12 +197,14 @@ struct MemberRef {
 // (a group's member array is written when the group is made and never by a kernel: its element is read through the CONSTANT address
 // space -- scalar loads the compiler may place where the values are used, like a single engine's kernel arguments, instead of global
 // loads at the kernel's head whose results it must keep alive, and spill, to the end: round-5 verdict, k_hosp_install<GROUP>'s scratch)
-static_assert(sizeof(MemberRef) % 8 == 0, "copied as 64-bit words");
-__device__ __forceinline__ void member_from_constant(MemberRef *out, const MemberRef *m) {
+// (generic in the element: the tree reports keep a table of their own, k_transmission.inc's TxMember)
+template <class T>
+__device__ __forceinline__ void member_from_constant(T *out, const T *m) {
+    static_assert(sizeof(T) % 8 == 0, "copied as 64-bit words");
     const CAS uint64_t *s = (const CAS uint64_t *)m;
     uint64_t *d = reinterpret_cast<uint64_t *>(out);
 #pragma unroll
-    for (size_t k = 0; k < sizeof(MemberRef) / 8; k++) d[k] = s[k];
+    for (size_t k = 0; k < sizeof(T) / 8; k++) d[k] = s[k];
 }
 #define MEMBER_OF_LAUNCH                                       \
     MemberRef mref_g_;                                         \

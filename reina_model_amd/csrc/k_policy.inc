@@ -1,5 +1,5 @@
 // reina_hip.hip part: triggered interventions (include/reina_policy.h; DESIGN.md section 6e).
-// Included at the end of reina_hip.hip (it uses the host helpers and the group above); not a standalone header.
+// Included at the end of reina_hip.hip (it uses the host helpers, the group and k_addons.inc above); not a standalone header.
 //
 // ONE launch a day, k_policy, queued ahead of the day's opening launch: blockIdx.y = member (the member table read through the
 // constant address space), POLICY_WGS workgroups a member.  Every wave sums the signal row of its member's counter block and
@@ -123,11 +123,7 @@ __global__ __launch_bounds__(POLICY_THREADS) void k_policy(const MemberRef *M_, 
     }
 }
 
-struct reina_policy {
-    reina_engine_t *e0 = nullptr;            // the engine, or the group's representative
-    reina_group *g = nullptr;                // a group's policy
-    std::vector<reina_engine_t *> members;
-    const MemberRef *d_refs = nullptr;       // the engine's / the group's member table (device)
+struct reina_policy : attachment {           // (last_day: the last day run)
     reina_policy_rule_t rule;
     PolicyEntry *d_bank = nullptr;           // [n_levels]
     std::vector<PolicyEntry> h_bank;         // the entries as derived on the host (LDS sizing; the members' mirrors after a run)
@@ -136,7 +132,6 @@ struct reina_policy {
     PolicyState *d_state[2] = {nullptr, nullptr};
     uint32_t parity = 0;                     // which copy of the state the next launch reads
     int32_t *d_trace = nullptr;              // [members][REINA_MAX_DAYS][REINA_POLICY_TRACE_WORDS]
-    int64_t last_day = -1;                   // the last day run
 };
 
 static void free_policy(reina_policy *p) {
@@ -183,19 +178,10 @@ static int policy_check_rule(const reina_policy_rule_t *r) {
 static int policy_create(const std::vector<reina_engine_t *> &members, reina_group *g, const MemberRef *d_refs,
                          const reina_policy_rule_t *rule, reina_policy_t **out) {
     if (!rule || !out) return REINA_E_INVALID;
-    for (auto m : members) {
-        if (!m->bound) return REINA_E_NOT_BOUND;
-        if (m->cfg.n_shards > 1 || m->exact || m->coll_fn || m->a2a_fn) {
-            g_last_error = "policy: sharded engines are refused (the signal would need the shards' all-reduce), exact attribution included";
-            return REINA_E_INVALID;
-        }
-    }
+    if (int rc = attachment_check_members(members, "policy", "the signal would need the shards' all-reduce")) return rc;
     if (int rc = policy_check_rule(rule)) return rc;
     reina_policy *p = new reina_policy();
-    p->e0 = members[0];
-    p->g = g;
-    p->members = members;
-    p->d_refs = d_refs;
+    p->e0 = members[0], p->g = g, p->members = members, p->d_refs = d_refs;
     p->rule = *rule;
     const size_t K = members.size(), L = rule->n_levels;
     p->h_bank.resize(L);
@@ -216,19 +202,12 @@ static int policy_create(const std::vector<reina_engine_t *> &members, reina_gro
 extern "C" {
 
 // ahead of a day's opening launch
-static int policy_launch_day(reina_policy *p, const reina_day_t &dp, hipStream_t s) {
-    if (dp.day >= REINA_MAX_DAYS) {
-        g_last_error = "day >= REINA_MAX_DAYS (4096): the winner-selection keys carry the day in 12 bits";
-        return REINA_E_INVALID;
-    }
+static int policy_launch_day(attachment *a, const reina_day_t &dp, hipStream_t s) {
+    reina_policy *p = static_cast<reina_policy *>(a);
+    if (int rc = attachment_check_day(dp.day)) return rc;
     const uint32_t K = (uint32_t)p->members.size();
-    if (K > 1)
-        hipLaunchKernelGGL(k_policy<true>, dim3(POLICY_WGS, K), dim3(POLICY_THREADS), 0, s, p->d_refs, p->e0->h_ref, p->rule, p->d_bank,
-                           p->d_state[p->parity], p->d_state[p->parity ^ 1u], p->d_trace, dp.day, p->new_bank ? 1u : 0u);
-    else
-        hipLaunchKernelGGL(k_policy<false>, dim3(POLICY_WGS, 1), dim3(POLICY_THREADS), 0, s, p->d_refs, p->e0->h_ref, p->rule, p->d_bank,
-                           p->d_state[p->parity], p->d_state[p->parity ^ 1u], p->d_trace, dp.day, p->new_bank ? 1u : 0u);
-    HIP_CHECK(hipGetLastError());
+    launch_members(k_policy, K > 1, POLICY_WGS, K, POLICY_THREADS, s, p->d_refs, p->e0->h_ref, p->rule, p->d_bank, p->d_state[p->parity],
+                   p->d_state[p->parity ^ 1u], p->d_trace, dp.day, p->new_bank ? 1u : 0u);
     p->parity ^= 1u;
     p->new_bank = false;
     p->last_day = dp.day;
@@ -286,32 +265,19 @@ int reina_policy_upload_level(reina_policy_t *p, uint32_t level, const reina_con
 }
 
 int reina_policy_run_days(reina_policy_t *p, const reina_day_t *days, uint32_t n_days, int32_t *history_base, void *stream) {
-    if (!p || !days) return REINA_E_INVALID;
-    if (p->g) {
-        g_last_error = "policy: made for a group -- run it with reina_group_policy_run_days";
-        return REINA_E_INVALID;
-    }
+    if (!days) return REINA_E_INVALID;
+    if (int rc = attachment_kind(p, false, "policy: reina_policy_run_days")) return rc;
     if (int rc = policy_begin_run(p)) return rc;
-    int rc = REINA_OK;
-    // (always the three-launch day: reina_step_day, never the several-days-in-one-launch form)
-    for (uint32_t k = 0; k < n_days && rc == REINA_OK; k++) {
-        reina_day_t d = days[k];
-        d.history_row = history_base ? history_base + (size_t)k * REINA_COUNTER_WORDS : nullptr;
-        rc = policy_launch_day(p, d, (hipStream_t)stream);
-        if (rc == REINA_OK) rc = reina_step_day(p->e0, &d, stream);
-    }
+    const int rc = engine_run_days(p->e0, days, n_days, history_base, stream, day_hooks{p, policy_launch_day, nullptr});
     policy_end_run(p);
     return rc;
 }
 
 int reina_group_policy_run_days(reina_policy_t *p, const reina_day_t *days, uint32_t n_days, int32_t *const *history_bases, void *stream) {
-    if (!p || !days) return REINA_E_INVALID;
-    if (!p->g) {
-        g_last_error = "policy: made for one engine -- run it with reina_policy_run_days";
-        return REINA_E_INVALID;
-    }
+    if (!days) return REINA_E_INVALID;
+    if (int rc = attachment_kind(p, true, "policy: reina_group_policy_run_days")) return rc;
     if (int rc = policy_begin_run(p)) return rc;
-    const int rc = group_run_days(p->g, days, n_days, history_bases, stream, p);
+    const int rc = group_run_days(p->g, days, n_days, history_bases, stream, day_hooks{p, policy_launch_day, nullptr});
     policy_end_run(p);
     return rc;
 }

@@ -1,5 +1,6 @@
 // reina_hip.hip part: transmission-tree reports of an unsharded engine between two days (include/reina_transmission.h;
-// DESIGN.md "Transmission reports").  Included at the end of reina_hip.hip (it uses the host helpers and the group above).
+// DESIGN.md "Transmission reports").  Included at the end of reina_hip.hip (it uses the host helpers, the group and
+// k_addons.inc above: the wave helpers, load_links, the age-group arguments and the launch geometry).
 //
 // A report reads the hot words and the cold records and writes nothing but the caller's scratch and report block.  Five kinds
 // of launch, each bound by memory bandwidth:
@@ -18,8 +19,8 @@
 // GROUP: the member is element blockIdx.y of a table read through the constant address space; otherwise `one_`, by value.
 #include "../../include/reina_transmission.h"
 
-#define TX_THREADS 256
-#define TX_TILE 512u
+#define TX_THREADS REPORT_THREADS
+#define TX_TILE REPORT_TILE
 #define TX_MARK 0xFFFFFFFFu        // parent of an agent that is not infected (and an empty hash slot)
 #define TX_ROOTED 0x80000000u      // distance word: the parent is a root
 #define TX_DIST_MAX 0x7FFFFFFFu    // distances saturate (a cycle of bad data doubles them every round)
@@ -41,12 +42,10 @@ struct TxMember {
     uint32_t *size;      // [n_agents] agents in the tree of each root
     uint64_t *report;    // [REINA_TX_REPORT_WORDS]
 };
-static_assert(sizeof(TxMember) % 8 == 0, "copied as 64-bit words");
 
 struct TxArgs {
-    uint32_t n_agents, nr_ages, host_rounds;   // host_rounds ~0: from the member's day word
-    int32_t age_start[REINA_MAX_AGES + 1];
-    uint8_t group[REINA_MAX_AGES];
+    AgeGroupArgs p;
+    uint32_t host_rounds;   // ~0: from the member's day word
 };
 
 // smallest r with 2^r >= max_depth + 1
@@ -60,10 +59,7 @@ template <bool GROUP>
 __device__ __forceinline__ TxMember tx_member(const TxMember *M_, const TxMember &one_) {
     if (!GROUP) return one_;
     TxMember m;
-    const CAS uint64_t *s = (const CAS uint64_t *)(M_ + blockIdx.y);
-    uint64_t *d = reinterpret_cast<uint64_t *>(&m);
-#pragma unroll
-    for (size_t k = 0; k < sizeof(TxMember) / 8; k++) d[k] = s[k];
+    member_from_constant(&m, M_ + blockIdx.y);
     return m;
 }
 
@@ -72,21 +68,6 @@ __device__ __forceinline__ uint32_t tx_member_rounds(const TxMember &m, const Tx
     int32_t day = m.counters[SC_IDX(REINA_S_DAY)];
     day = day < 0 ? 0 : (day > (int32_t)REINA_MAX_DAYS ? (int32_t)REINA_MAX_DAYS : day);
     return tx_rounds((uint64_t)day + 1u);
-}
-
-// +1 in LDS histogram cell b of every lane with b >= 0; the lanes that share the first such lane's cell add once.
-// Called by whole waves.
-__device__ __forceinline__ void tx_count(uint32_t *hist, int b) {
-    const uint64_t act = __ballot(b >= 0);
-    if (!act) return;
-    const int lead = __ffsll((unsigned long long)act) - 1;
-    const int lb = __shfl(b, lead);
-    const uint64_t same = __ballot(b == lb);
-    if (b == lb) {
-        if ((int)(threadIdx.x & 63u) == lead) atomicAdd(&hist[lb], (uint32_t)__popcll(same));
-    } else if (b >= 0) {
-        atomicAdd(&hist[b], 1u);
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -100,90 +81,57 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_links(const TxMember *M_, con
     __shared__ int32_t s_as[REINA_MAX_AGES + 1];
     __shared__ uint8_t s_grp[REINA_MAX_AGES];
     const TxMember m = tx_member<GROUP>(M_, one_);
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const GAS uint32_t *hot = (const GAS uint32_t *)m.hot;
+    const GAS reina_cold_t *cold = (const GAS reina_cold_t *)m.cold;
+    GAS uint64_t *pairs = (GAS uint64_t *)m.pairs;
+    GAS uint32_t *size = (GAS uint32_t *)m.size;
+    const uint32_t tid = threadIdx.x;
     for (uint32_t k = tid; k < TX_CELLS; k += TX_THREADS) s_off[k] = 0u;
     for (uint32_t k = tid; k < TX_MATRIX_CELLS; k += TX_THREADS) s_mat[k] = 0u;
     if (tid < TX_SUMS) s_sum[tid] = s_sq[tid] = 0ull;
     if (tid < 4) s_cnt[tid] = 0u;
-    if (tid <= REINA_MAX_AGES) s_as[tid] = a.age_start[tid];
-    if (tid < REINA_MAX_AGES) s_grp[tid] = a.group[tid];
+    if (tid <= REINA_MAX_AGES) s_as[tid] = a.p.age_start[tid];
+    if (tid < REINA_MAX_AGES) s_grp[tid] = a.p.group[tid];
     __syncthreads();
-    const uint32_t N = a.n_agents, tiles = (N + TX_TILE - 1u) / TX_TILE;
-    const int top = (int)a.nr_ages - 1;
-    uint64_t *pairs = m.pairs;
+    const uint32_t N = a.p.n_agents, tiles = (N + TX_TILE - 1u) / TX_TILE;
+    const int top = (int)a.p.nr_ages - 1;
     for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
-        uint32_t idx[2], w[2];
-        bool inf[2];
+        Links l;
+        load_links<false>(l, t, N, hot, cold, nullptr, s_cnt, 0, 1, 2, 3);   // (a tile without infected agents still writes its pairs)
 #pragma unroll
         for (int j = 0; j < 2; j++) {
-            idx[j] = t * TX_TILE + (uint32_t)j * TX_THREADS + tid;
-            w[j] = idx[j] < N ? m.hot[idx[j]] : 0u;
-            inf[j] = RH_STATE(w[j]) != RS_SUSCEPTIBLE;
-        }
-        int32_t src[2] = {-1, -1};
-        uint32_t n[2] = {0u, 0u};
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            if (inf[j]) {
-                const v2u_ c = *reinterpret_cast<const v2u_ *>(&m.cold[idx[j]].infector);   // infector, n_infected
-                src[j] = (int32_t)c.x;
-                n[j] = c.y;
+            const uint32_t i = l.idx[j], w = l.w[j], n = l.n[j], st = RH_STATE(w), v = RH_VARIANT(w);
+            const uint32_t sev = RH_SEV(w) < 4u ? RH_SEV(w) : 4u;
+            const uint32_t o = st <= RS_IN_ICU ? 0u : ((w & RH_INCLUDED) ? 1u : 2u);
+            const uint32_t det = (w & RH_DETECTED) ? 1u : 0u;
+            wave_count(s_off, l.inf[j] ? (int)((((v * REINA_TX_SEVERITIES + sev) * REINA_TX_OUTCOMES + o) * 2u + det) * REINA_TX_BINS +
+                                               (n < REINA_TX_BINS - 1u ? n : REINA_TX_BINS - 1u))
+                                       : -1);
+            if (l.inf[j] && n) {
+                atomicAdd(&s_sum[v * REINA_TX_OUTCOMES + o], (unsigned long long)n);
+                atomicAdd(&s_sq[v * REINA_TX_OUTCOMES + o], (unsigned long long)n * n);
             }
-        }
-        uint32_t sw[2] = {0u, 0u};
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-            if (inf[j] && src[j] >= 0 && (uint32_t)src[j] < N && (uint32_t)src[j] != idx[j]) sw[j] = m.hot[src[j]];
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const uint32_t i = idx[j], st = RH_STATE(w[j]), v = RH_VARIANT(w[j]);
-            const uint32_t sev = RH_SEV(w[j]) < 4u ? RH_SEV(w[j]) : 4u;
-            const uint32_t o = st <= RS_IN_ICU ? 0u : ((w[j] & RH_INCLUDED) ? 1u : 2u);
-            const uint32_t det = (w[j] & RH_DETECTED) ? 1u : 0u;
-            const bool root = inf[j] && src[j] == -1;
-            const bool linked = inf[j] && !root && RH_STATE(sw[j]) != RS_SUSCEPTIBLE;   // (sw = 0 for an infector out of range or itself)
-            const bool bad = inf[j] && !root && !linked;
-            tx_count(s_off, inf[j] ? (int)((((v * REINA_TX_SEVERITIES + sev) * REINA_TX_OUTCOMES + o) * 2u + det) * REINA_TX_BINS +
-                                           (n[j] < REINA_TX_BINS - 1u ? n[j] : REINA_TX_BINS - 1u))
-                                   : -1);
-            if (inf[j] && n[j]) {
-                atomicAdd(&s_sum[v * REINA_TX_OUTCOMES + o], (unsigned long long)n[j]);
-                atomicAdd(&s_sq[v * REINA_TX_OUTCOMES + o], (unsigned long long)n[j] * n[j]);
-            }
-            if (linked) {
-                const uint32_t gs = s_grp[age_of(s_as, i, 0, top)], gi = s_grp[age_of(s_as, (uint32_t)src[j], 0, top)];
+            if (l.linked[j]) {
+                const uint32_t gs = s_grp[age_of(s_as, i, 0, top)], gi = s_grp[age_of(s_as, (uint32_t)l.src[j], 0, top)];
                 atomicAdd(&s_mat[(v * REINA_TX_MAX_GROUPS + gi) * REINA_TX_MAX_GROUPS + gs], 1u);
             }
-            const uint32_t ci = (uint32_t)__popcll(__ballot(inf[j])), cr = (uint32_t)__popcll(__ballot(root));
-            const uint32_t cl = (uint32_t)__popcll(__ballot(linked)), cb = (uint32_t)__popcll(__ballot(bad));
-            if (lane == 0) {
-                if (ci) atomicAdd(&s_cnt[0], ci);
-                if (cr) atomicAdd(&s_cnt[1], cr);
-                if (cl) atomicAdd(&s_cnt[2], cl);
-                if (cb) atomicAdd(&s_cnt[3], cb);
-            }
             if (i < N) {
-                const uint64_t p = !inf[j] ? (uint64_t)TX_MARK
-                                 : linked  ? ((uint64_t)(uint32_t)src[j] | (1ull << 32))
-                                           : ((uint64_t)i | ((uint64_t)TX_ROOTED << 32));
-                pairs[i] = p;
-                m.size[i] = 0u;
+                pairs[i] = !l.inf[j]     ? (uint64_t)TX_MARK
+                           : l.linked[j] ? ((uint64_t)(uint32_t)l.src[j] | (1ull << 32))
+                                         : ((uint64_t)i | ((uint64_t)TX_ROOTED << 32));
+                size[i] = 0u;
             }
         }
     }
     __syncthreads();
-    uint64_t *R = m.report;
-    for (uint32_t k = tid; k < TX_CELLS; k += TX_THREADS)
-        if (s_off[k]) atomicAdd((unsigned long long *)&R[REINA_TX_OFFSPRING + k], (unsigned long long)s_off[k]);
-    for (uint32_t k = tid; k < TX_MATRIX_CELLS; k += TX_THREADS)
-        if (s_mat[k]) atomicAdd((unsigned long long *)&R[REINA_TX_MATRIX + k], (unsigned long long)s_mat[k]);
-    if (tid < TX_SUMS) {
-        if (s_sum[tid]) atomicAdd((unsigned long long *)&R[REINA_TX_OFFSPRING_SUM + tid], s_sum[tid]);
-        if (s_sq[tid]) atomicAdd((unsigned long long *)&R[REINA_TX_OFFSPRING_SUMSQ + tid], s_sq[tid]);
-    }
+    GAS unsigned long long *R = (GAS unsigned long long *)m.report;
+    flush_lds(s_off, TX_CELLS, R + REINA_TX_OFFSPRING);
+    flush_lds(s_mat, TX_MATRIX_CELLS, R + REINA_TX_MATRIX);
+    flush_lds(s_sum, TX_SUMS, R + REINA_TX_OFFSPRING_SUM);
+    flush_lds(s_sq, TX_SUMS, R + REINA_TX_OFFSPRING_SUMSQ);
     if (tid < 4 && s_cnt[tid]) {
         const uint32_t at[4] = {REINA_TX_S_N_INFECTED_AGENTS, REINA_TX_S_N_ROOTS, REINA_TX_S_N_LINKED, REINA_TX_S_BAD_LINKS};
-        atomicAdd((unsigned long long *)&R[REINA_TX_SCALARS + at[tid]], (unsigned long long)s_cnt[tid]);
+        atomicAdd(&R[REINA_TX_SCALARS + at[tid]], (unsigned long long)s_cnt[tid]);
     }
 }
 
@@ -192,7 +140,7 @@ template <bool GROUP>
 __global__ __launch_bounds__(TX_THREADS) void k_tx_jump(const TxMember *M_, const TxMember one_, const TxArgs a, uint32_t r) {
     const TxMember m = tx_member<GROUP>(M_, one_);
     if (r >= tx_member_rounds(m, a)) return;
-    const uint32_t N = a.n_agents;
+    const uint32_t N = a.p.n_agents;
     const uint64_t *src = m.pairs + (size_t)(r & 1u) * N;
     uint64_t *dst = m.pairs + (size_t)((r + 1u) & 1u) * N;
     for (uint32_t i = blockIdx.x * TX_THREADS + threadIdx.x; i < N; i += gridDim.x * TX_THREADS) {
@@ -239,7 +187,7 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_tally(const TxMember *M_, con
     }
     if (tid == 0) s_unconv = s_maxgen = 0u;
     __syncthreads();
-    const uint32_t N = a.n_agents;
+    const uint32_t N = a.p.n_agents;
     const uint64_t *pairs = m.pairs + (size_t)(tx_member_rounds(m, a) & 1u) * N;
     const uint32_t stride = gridDim.x * TX_THREADS;
     const uint32_t end = (N + TX_THREADS - 1u) / TX_THREADS * TX_THREADS;   // (whole waves run the loop)
@@ -254,13 +202,9 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_tally(const TxMember *M_, con
         const bool infected = parent != TX_MARK;
         const bool conv = infected && (d & TX_ROOTED) && parent < N;   // (every pair of an infected agent points below N)
         const uint32_t gen = d & TX_DIST_MAX;
-        tx_count(s_gen, conv ? (int)(RH_VARIANT(w) * REINA_TX_GENERATIONS + (gen < 255u ? gen : 255u)) : -1);
+        wave_count(s_gen, conv ? (int)(RH_VARIANT(w) * REINA_TX_GENERATIONS + (gen < 255u ? gen : 255u)) : -1);
         const uint32_t nu = (uint32_t)__popcll(__ballot(infected && !conv));
-        uint32_t g = conv ? gen : 0u;
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint32_t o = (uint32_t)__shfl_xor((int)g, off);
-            g = o > g ? o : g;
-        }
+        const uint32_t g = wave_max(conv ? gen : 0u);
         if (lane == 0) {
             if (nu) atomicAdd(&s_unconv, nu);
             if (g) atomicMax(&s_maxgen, g);
@@ -280,14 +224,13 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_tally(const TxMember *M_, con
         }
     }
     __syncthreads();
-    uint64_t *R = m.report;
+    GAS unsigned long long *R = (GAS unsigned long long *)m.report;
     for (uint32_t k = tid; k < TX_HASH; k += TX_THREADS)
         if (s_key[k] != TX_MARK) atomicAdd(&m.size[s_key[k]], s_cnt[k]);
-    for (uint32_t k = tid; k < REINA_TX_VARIANTS * REINA_TX_GENERATIONS; k += TX_THREADS)
-        if (s_gen[k]) atomicAdd((unsigned long long *)&R[REINA_TX_GENERATION + k], (unsigned long long)s_gen[k]);
+    flush_lds(s_gen, REINA_TX_VARIANTS * REINA_TX_GENERATIONS, R + REINA_TX_GENERATION);
     if (tid == 0) {
-        if (s_unconv) atomicAdd((unsigned long long *)&R[REINA_TX_SCALARS + REINA_TX_S_UNCONVERGED], (unsigned long long)s_unconv);
-        if (s_maxgen) atomicMax((unsigned long long *)&R[REINA_TX_SCALARS + REINA_TX_S_MAX_GENERATION], (unsigned long long)s_maxgen);
+        if (s_unconv) atomicAdd(&R[REINA_TX_SCALARS + REINA_TX_S_UNCONVERGED], (unsigned long long)s_unconv);
+        if (s_maxgen) atomicMax(&R[REINA_TX_SCALARS + REINA_TX_S_MAX_GENERATION], (unsigned long long)s_maxgen);
     }
 }
 
@@ -305,7 +248,7 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_clusters(const TxMember *M_, 
     }
     if (tid == 0) s_key = 0ull;
     __syncthreads();
-    const uint32_t N = a.n_agents;
+    const uint32_t N = a.p.n_agents;
     const uint32_t stride = gridDim.x * TX_THREADS;
     const uint32_t end = (N + TX_THREADS - 1u) / TX_THREADS * TX_THREADS;
     for (uint32_t i = blockIdx.x * TX_THREADS + tid; i < end; i += stride) {
@@ -317,20 +260,14 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_clusters(const TxMember *M_, 
             atomicAdd(&s_ca[bin], (unsigned long long)s);
             key = ((unsigned long long)s << 32) | (unsigned long long)(~i);
         }
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)key, off), hi = (uint32_t)__shfl_xor((int)(uint32_t)(key >> 32), off);
-            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-            key = o > key ? o : key;
-        }
+        key = wave_max(key);
         if (lane == 0 && key) atomicMax(&s_key, key);
     }
     __syncthreads();
-    uint64_t *R = m.report;
-    if (tid < REINA_TX_CLUSTER_BINS && s_cl[tid]) {
-        atomicAdd((unsigned long long *)&R[REINA_TX_CLUSTERS + tid], (unsigned long long)s_cl[tid]);
-        atomicAdd((unsigned long long *)&R[REINA_TX_CLUSTER_AGENTS + tid], s_ca[tid]);
-    }
-    if (tid == 0 && s_key) atomicMax((unsigned long long *)&R[REINA_TX_SCALARS + REINA_TX_S_LARGEST_KEY], s_key);
+    GAS unsigned long long *R = (GAS unsigned long long *)m.report;
+    flush_lds(s_cl, REINA_TX_CLUSTER_BINS, R + REINA_TX_CLUSTERS);
+    flush_lds(s_ca, REINA_TX_CLUSTER_BINS, R + REINA_TX_CLUSTER_AGENTS);
+    if (tid == 0 && s_key) atomicMax(&R[REINA_TX_SCALARS + REINA_TX_S_LARGEST_KEY], s_key);
 }
 
 // k_tx_finish: one lane per member (grid.y)
@@ -362,23 +299,8 @@ static int tx_engine_ok(const reina_engine_t *e) {
 }
 
 static int tx_args(const reina_engine_t *e, const uint8_t *age_group, uint32_t n_groups, uint32_t max_depth, TxArgs *a) {
-    if (!age_group || n_groups < 1u || n_groups > REINA_TX_MAX_GROUPS) {
-        g_last_error = "reina_tx_report: age_group must be a table of groups, 1 <= n_groups <= REINA_TX_MAX_GROUPS";
-        return REINA_E_INVALID;
-    }
-    std::memset(a, 0, sizeof(*a));
-    a->n_agents = e->cfg.n_agents;
-    a->nr_ages = e->cfg.nr_ages;
     a->host_rounds = max_depth ? tx_rounds(max_depth) : 0xFFFFFFFFu;
-    std::memcpy(a->age_start, e->cfg.age_start, sizeof(a->age_start));
-    for (uint32_t k = 0; k < e->cfg.nr_ages; k++) {
-        if (age_group[k] >= n_groups) {
-            g_last_error = "reina_tx_report: an age's group is not below n_groups";
-            return REINA_E_INVALID;
-        }
-        a->group[k] = age_group[k];
-    }
-    return REINA_OK;
+    return age_group_args(e, age_group, n_groups, REINA_TX_MAX_GROUPS, "reina_tx_report", &a->p);
 }
 
 static bool tx_aligned(const void *p) { return p && ((uintptr_t)p & 15u) == 0u; }
@@ -394,30 +316,20 @@ static TxMember tx_member_of(const reina_engine_t *e, void *scratch, uint64_t *r
     return m;
 }
 
-// every pass of a report: members = 1 (`one`) or the K members of the device table `d_m`
-template <bool GROUP>
+// every pass of a report: the K members of the device table `d_m`, or (d_m = nullptr) the one member `one`
 static int tx_launch(const TxMember *d_m, const TxMember &one, const TxArgs &a, uint32_t K, uint32_t n_cus, uint64_t *report, hipStream_t s) {
     HIP_CHECK(hipMemsetAsync(report, 0, (size_t)K * REINA_TX_REPORT_WORDS * 8u, s));
-    const uint32_t N = a.n_agents;
+    const uint32_t N = a.p.n_agents;
     const uint32_t tiles = (N + TX_TILE - 1u) / TX_TILE, waves = (N + TX_THREADS - 1u) / TX_THREADS;
-    uint32_t per = 4u * n_cus / K;   // workgroups per member of the passes that flush LDS tables
-    if (per < 1u) per = 1u;
-    const uint32_t g_links = tiles < per ? (tiles ? tiles : 1u) : per;
-    const uint32_t g_tally = waves < per ? (waves ? waves : 1u) : per;
+    // (four workgroups a compute unit in the passes that flush LDS tables)
+    const uint32_t g_links = member_grid(n_cus, K, tiles, 4u), g_tally = member_grid(n_cus, K, waves, 4u);
     const uint32_t g_jump = waves < 32768u ? (waves ? waves : 1u) : 32768u;
-    hipLaunchKernelGGL((k_tx_links<GROUP>), dim3(g_links, K), dim3(TX_THREADS), 0, s, d_m, one, a);
-    HIP_CHECK(hipGetLastError());
+    launch_members(k_tx_links, d_m, g_links, K, TX_THREADS, s, d_m, one, a);
     const uint32_t rounds = a.host_rounds != 0xFFFFFFFFu ? a.host_rounds : TX_DAY_ROUNDS;
-    for (uint32_t r = 0; r < rounds; r++) {
-        hipLaunchKernelGGL((k_tx_jump<GROUP>), dim3(g_jump, K), dim3(TX_THREADS), 0, s, d_m, one, a, r);
-        HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL((k_tx_tally<GROUP>), dim3(g_tally, K), dim3(TX_THREADS), 0, s, d_m, one, a);
-    HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL((k_tx_clusters<GROUP>), dim3(g_tally, K), dim3(TX_THREADS), 0, s, d_m, one, a);
-    HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL((k_tx_finish<GROUP>), dim3(1, K), dim3(64), 0, s, d_m, one, a);
-    HIP_CHECK(hipGetLastError());
+    for (uint32_t r = 0; r < rounds; r++) launch_members(k_tx_jump, d_m, g_jump, K, TX_THREADS, s, d_m, one, a, r);
+    launch_members(k_tx_tally, d_m, g_tally, K, TX_THREADS, s, d_m, one, a);
+    launch_members(k_tx_clusters, d_m, g_tally, K, TX_THREADS, s, d_m, one, a);
+    launch_members(k_tx_finish, d_m, 1u, K, 64, s, d_m, one, a);
     return REINA_OK;
 }
 
@@ -434,7 +346,7 @@ int reina_tx_report(reina_engine_t *e, const uint8_t *age_group, uint32_t n_grou
     }
     TxArgs a;
     if (int rc = tx_args(e, age_group, n_groups, max_depth, &a)) return rc;
-    return tx_launch<false>(nullptr, tx_member_of(e, dev_scratch, dev_report), a, 1u, e->n_cus, dev_report, (hipStream_t)stream);
+    return tx_launch(nullptr, tx_member_of(e, dev_scratch, dev_report), a, 1u, e->n_cus, dev_report, (hipStream_t)stream);
 }
 
 int reina_group_tx_report(reina_group_t *g, const uint8_t *age_group, uint32_t n_groups, uint32_t max_depth,
@@ -464,7 +376,7 @@ int reina_group_tx_report(reina_group_t *g, const uint8_t *age_group, uint32_t n
         g_last_error = "reina_group_tx_report: member table upload failed";
         rc = REINA_E_HIP;
     }
-    if (rc == REINA_OK) rc = tx_launch<true>(d_m, h[0], a, K, g->members[0]->n_cus, dev_report, s);
+    if (rc == REINA_OK) rc = tx_launch(d_m, h[0], a, K, g->members[0]->n_cus, dev_report, s);
     // (the member table and its host copy live until the passes have run)
     const hipError_t se = hipStreamSynchronize(s);
     (void)hipFree(d_m);

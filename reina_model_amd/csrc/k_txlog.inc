@@ -1,5 +1,5 @@
 // reina_hip.hip part: the dated transmission log (include/reina_txlog.h; DESIGN.md section 6f).
-// Included at the end of reina_hip.hip (it uses the host helpers, the group and k_transmission.inc's tx_count above).
+// Included at the end of reina_hip.hip (it uses the host helpers, the group and k_addons.inc above).
 //
 // Three kernels, each bound by memory traffic:
 //   k_txlog_begin   streams the hot words (16 bytes a lane) and writes every log word.
@@ -23,8 +23,8 @@
 // kernel boundary lies on either side of every launch).
 #include "../../include/reina_txlog.h"
 
-#define TXL_THREADS 256
-#define TXL_TILE 512u
+#define TXL_THREADS REPORT_THREADS
+#define TXL_TILE REPORT_TILE
 #define TXL_NONE ((uint32_t)REINA_TXLOG_NONE)
 #define TXL_BEFORE ((uint32_t)REINA_TXLOG_BEFORE)
 static_assert(REINA_MAX_DAYS < REINA_TXLOG_BEFORE, "day numbers lie below the codes");
@@ -32,9 +32,8 @@ static_assert(REINA_TXLOG_FIXED_WORDS == 1312u && REINA_TXLOG_DAY_WORDS == 80u, 
 static_assert(REINA_TXLOG_VARIANTS == REINA_MAX_VARIANTS && REINA_TXLOG_MAX_GROUPS == REINA_TX_MAX_GROUPS, "RH_VARIANT has two bits; the groups are the tree reports'");
 
 struct TxlArgs {
-    uint32_t n_agents, nr_ages, n_days, pad_;
-    int32_t age_start[REINA_MAX_AGES + 1];
-    uint8_t group[REINA_MAX_AGES];
+    AgeGroupArgs p;
+    uint32_t n_days;
 };
 
 __host__ __device__ __forceinline__ uint32_t txl_begin_word(uint32_t w) {
@@ -110,27 +109,6 @@ __global__ __launch_bounds__(TXL_THREADS) void k_txlog_day(const MemberRef *M_, 
     }
 }
 
-// val into cell `key` of a table in global memory for every lane with key >= 0: the lanes that share the first such lane's
-// cell add their sum once.  Called by whole waves.
-__device__ __forceinline__ void txl_add(GAS unsigned long long *tab, int key, unsigned long long val) {
-    const uint64_t act = __ballot(key >= 0);
-    if (!act) return;
-    const int lead = __ffsll((unsigned long long)act) - 1;
-    const int lk = __shfl(key, lead);
-    const bool same = key == lk;
-    unsigned long long s = same ? val : 0ull;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)s, off), hi = (uint32_t)__shfl_xor((int)(uint32_t)(s >> 32), off);
-        s += ((unsigned long long)hi << 32) | lo;
-    }
-    if (same) {
-        if ((int)(threadIdx.x & 63u) == lead && s) atomicAdd(&tab[lk], s);
-    } else if (key >= 0 && val) {
-        atomicAdd(&tab[key], val);
-    }
-}
-
 __device__ __forceinline__ int txl_clip(int x, int hi) { return x < 0 ? 0 : (x > hi ? hi : x); }
 
 // 256 threads, tiles of 512 agents (two per thread), the workgroup's tiles strided over the grid
@@ -149,108 +127,70 @@ __global__ __launch_bounds__(TXL_THREADS) void k_txlog_report(const MemberRef *M
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     for (uint32_t k = tid; k < REINA_TXLOG_SCALARS; k += TXL_THREADS) s_h[k] = 0u;
     if (tid < REINA_TXLOG_S_NR) s_c[tid] = tid == REINA_TXLOG_S_FIRST_DAY ? 0xFFFFFFFFu : 0u;
-    if (tid <= REINA_MAX_AGES) s_as[tid] = a.age_start[tid];
-    if (tid < REINA_MAX_AGES) s_grp[tid] = a.group[tid];
+    if (tid <= REINA_MAX_AGES) s_as[tid] = a.p.age_start[tid];
+    if (tid < REINA_MAX_AGES) s_grp[tid] = a.p.group[tid];
     __syncthreads();
-    const uint32_t N = a.n_agents, D = a.n_days, tiles = (N + TXL_TILE - 1u) / TXL_TILE;
-    const int top = (int)a.nr_ages - 1;
+    const uint32_t N = a.p.n_agents, D = a.n_days, tiles = (N + TXL_TILE - 1u) / TXL_TILE;
+    const int top = (int)a.p.nr_ages - 1;
     GAS unsigned long long *inc_t = R + REINA_TXLOG_INCIDENCE(D), *ons_t = R + REINA_TXLOG_ONSETS(D), *coh_t = R + REINA_TXLOG_COHORT(D);
     for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
-        uint32_t idx[2], w[2], lw[2];
-        bool inf[2];
+        Links l;
+        if (!load_links<true>(l, t, N, hot, cold, L, s_c, REINA_TXLOG_S_INFECTED, -1, REINA_TXLOG_S_LINKS, REINA_TXLOG_S_BAD_LINKS)) continue;
 #pragma unroll
         for (int j = 0; j < 2; j++) {
-            idx[j] = t * TXL_TILE + (uint32_t)j * TXL_THREADS + tid;
-            w[j] = idx[j] < N ? hot[idx[j]] : 0u;
-            lw[j] = idx[j] < N ? L[idx[j]] : 0u;
-            inf[j] = RH_STATE(w[j]) != RS_SUSCEPTIBLE;
-        }
-        if (!__ballot(inf[0] || inf[1])) continue;
-        int32_t src[2] = {-1, -1};
-        uint32_t n[2] = {0u, 0u};
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            if (inf[j]) {
-                const v2u_ c = *reinterpret_cast<const GAS v2u_ *>(&cold[idx[j]].infector);   // infector, n_infected
-                src[j] = (int32_t)c.x;
-                n[j] = c.y;
-            }
-        }
-        uint32_t sw[2] = {0u, 0u}, sl[2] = {0u, 0u};
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-            if (inf[j] && src[j] >= 0 && (uint32_t)src[j] < N && (uint32_t)src[j] != idx[j]) {
-                sw[j] = hot[src[j]];
-                sl[j] = L[src[j]];
-            }
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const uint32_t i = idx[j], v = RH_VARIANT(w[j]);
-            const uint32_t ti = lw[j] & 0xFFFFu, oi = lw[j] >> 16;
-            const bool tk = inf[j] && ti < TXL_BEFORE, ok = inf[j] && oi < TXL_BEFORE;
-            const bool root = inf[j] && src[j] == -1;
-            const bool linked = inf[j] && !root && RH_STATE(sw[j]) != RS_SUSCEPTIBLE;   // (sw = 0 for an infector out of range or itself)
-            const bool bad = inf[j] && !root && !linked;
-            const uint32_t ts = sl[j] & 0xFFFFu, os = sl[j] >> 16;
-            const bool tsk = linked && ts < TXL_BEFORE, osk = linked && os < TXL_BEFORE;
+            const uint32_t i = l.idx[j], w = l.w[j], v = RH_VARIANT(w);
+            const uint32_t ti = l.lw[j] & 0xFFFFu, oi = l.lw[j] >> 16;
+            const bool tk = l.inf[j] && ti < TXL_BEFORE, ok = l.inf[j] && oi < TXL_BEFORE;
+            const uint32_t ts = l.sl[j] & 0xFFFFu, os = l.sl[j] >> 16;
+            const bool linked = l.linked[j], tsk = linked && ts < TXL_BEFORE, osk = linked && os < TXL_BEFORE;
             const bool both = tk && tsk;
             // the scalars: one LDS atomic a wave and kind
             const uint32_t oor = (tk && ti >= D ? 1u : 0u) + (ok && oi >= D ? 1u : 0u);
-            const uint32_t cnt[9] = {(uint32_t)__popcll(__ballot(inf[j])), (uint32_t)__popcll(__ballot(tk)),
-                                     (uint32_t)__popcll(__ballot(inf[j] && ti == TXL_BEFORE)), (uint32_t)__popcll(__ballot(ok)),
-                                     (uint32_t)__popcll(__ballot(linked)), (uint32_t)__popcll(__ballot(both)),
+            const uint32_t cnt[6] = {(uint32_t)__popcll(__ballot(tk)), (uint32_t)__popcll(__ballot(l.inf[j] && ti == TXL_BEFORE)),
+                                     (uint32_t)__popcll(__ballot(ok)), (uint32_t)__popcll(__ballot(both)),
                                      (uint32_t)__popcll(__ballot(both && ti <= ts)),
-                                     (uint32_t)__popcll(__ballot(oor >= 1u)) + (uint32_t)__popcll(__ballot(oor == 2u)),
-                                     (uint32_t)__popcll(__ballot(bad))};
-            uint32_t lo = tk ? ti : 0xFFFFFFFFu, hi = tk ? ti : 0u;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const uint32_t a_ = (uint32_t)__shfl_xor((int)lo, off), b_ = (uint32_t)__shfl_xor((int)hi, off);
-                lo = a_ < lo ? a_ : lo;
-                hi = b_ > hi ? b_ : hi;
-            }
+                                     (uint32_t)__popcll(__ballot(oor >= 1u)) + (uint32_t)__popcll(__ballot(oor == 2u))};
+            const uint32_t lo = wave_min(tk ? ti : 0xFFFFFFFFu), hi = wave_max(tk ? ti : 0u);
             if (lane == 0) {
-                const uint32_t at[9] = {REINA_TXLOG_S_INFECTED, REINA_TXLOG_S_DATED, REINA_TXLOG_S_BEFORE, REINA_TXLOG_S_WITH_ONSET,
-                                        REINA_TXLOG_S_LINKS, REINA_TXLOG_S_LINKS_DATED, REINA_TXLOG_S_GENERATION_NONPOSITIVE,
-                                        REINA_TXLOG_S_OUT_OF_RANGE, REINA_TXLOG_S_BAD_LINKS};
+                const uint32_t at[6] = {REINA_TXLOG_S_DATED, REINA_TXLOG_S_BEFORE, REINA_TXLOG_S_WITH_ONSET, REINA_TXLOG_S_LINKS_DATED,
+                                        REINA_TXLOG_S_GENERATION_NONPOSITIVE, REINA_TXLOG_S_OUT_OF_RANGE};
 #pragma unroll
-                for (int k = 0; k < 9; k++)
+                for (int k = 0; k < 6; k++)
                     if (cnt[k]) atomicAdd(&s_c[at[k]], cnt[k]);
-                if (cnt[1]) {
+                if (cnt[0]) {
                     atomicMin(&s_c[REINA_TXLOG_S_FIRST_DAY], lo);
                     atomicMax(&s_c[REINA_TXLOG_S_LAST_DAY], hi);
                 }
             }
             // the interval histograms (LDS)
-            tx_count(s_h, tk && ok ? (int)(REINA_TXLOG_INCUBATION + v * REINA_TXLOG_INCUBATION_BINS) +
+            wave_count(s_h, tk && ok ? (int)(REINA_TXLOG_INCUBATION + v * REINA_TXLOG_INCUBATION_BINS) +
                                          txl_clip((int)oi - (int)ti, REINA_TXLOG_INCUBATION_BINS - 1)
                                    : -1);
-            tx_count(s_h, both ? (int)(REINA_TXLOG_GENERATION + v * REINA_TXLOG_GENERATION_BINS) +
+            wave_count(s_h, both ? (int)(REINA_TXLOG_GENERATION + v * REINA_TXLOG_GENERATION_BINS) +
                                      txl_clip((int)ti - (int)ts, REINA_TXLOG_GENERATION_BINS - 1)
                                : -1);
-            tx_count(s_h, ok && osk ? (int)(REINA_TXLOG_SERIAL + v * REINA_TXLOG_SERIAL_BINS) +
+            wave_count(s_h, ok && osk ? (int)(REINA_TXLOG_SERIAL + v * REINA_TXLOG_SERIAL_BINS) +
                                           txl_clip((int)oi - (int)os + REINA_TXLOG_SERIAL_SHIFT, REINA_TXLOG_SERIAL_BINS - 1)
                                     : -1);
-            tx_count(s_h, tk && osk ? (int)(REINA_TXLOG_TOST + v * REINA_TXLOG_TOST_BINS) +
+            wave_count(s_h, tk && osk ? (int)(REINA_TXLOG_TOST + v * REINA_TXLOG_TOST_BINS) +
                                           txl_clip((int)ti - (int)os + REINA_TXLOG_TOST_SHIFT, REINA_TXLOG_TOST_BINS - 1)
                                     : -1);
             const uint32_t phase = tk && osk ? (ti < os ? 0u : 1u) : (tk && os == TXL_NONE ? 2u : 3u);
-            tx_count(s_h, linked ? (int)(REINA_TXLOG_LINK_PHASE + v * REINA_TXLOG_PHASES + phase) : -1);
+            wave_count(s_h, linked ? (int)(REINA_TXLOG_LINK_PHASE + v * REINA_TXLOG_PHASES + phase) : -1);
             // the tables by day (global, aggregated in the wave)
             const bool in = tk && ti < D;
             int g = 0;
             if (in) g = (int)s_grp[age_of(s_as, i, 0, top)];
-            txl_add(inc_t, in ? (int)((ti * REINA_TXLOG_VARIANTS + v) * REINA_TXLOG_MAX_GROUPS) + g : -1, 1ull);
-            txl_add(ons_t, ok && oi < D ? (int)(oi * REINA_TXLOG_VARIANTS + v) : -1, 1ull);
+            wave_add(inc_t, in ? (int)((ti * REINA_TXLOG_VARIANTS + v) * REINA_TXLOG_MAX_GROUPS) + g : -1, 1ull);
+            wave_add(ons_t, ok && oi < D ? (int)(oi * REINA_TXLOG_VARIANTS + v) : -1, 1ull);
             const int ck = in ? (int)((ti * REINA_TXLOG_VARIANTS + v) * REINA_TXLOG_COHORT_FIELDS) : -1;
-            txl_add(coh_t, ck, 1ull);
-            txl_add(coh_t + 1, ck, (unsigned long long)n[j]);
-            txl_add(coh_t + 2, ck, RH_STATE(w[j]) >= RS_RECOVERED ? 1ull : 0ull);
+            wave_add(coh_t, ck, 1ull);
+            wave_add(coh_t + 1, ck, (unsigned long long)l.n[j]);
+            wave_add(coh_t + 2, ck, RH_STATE(w) >= RS_RECOVERED ? 1ull : 0ull);
         }
     }
     __syncthreads();
-    for (uint32_t k = tid; k < REINA_TXLOG_SCALARS; k += TXL_THREADS)
-        if (s_h[k]) atomicAdd(&R[k], (unsigned long long)s_h[k]);
+    flush_lds(s_h, REINA_TXLOG_SCALARS, R);
     if (tid < REINA_TXLOG_S_NR) {
         GAS unsigned long long *S = R + REINA_TXLOG_SCALARS;
         if (tid == REINA_TXLOG_S_FIRST_DAY) {
@@ -266,15 +206,10 @@ __global__ __launch_bounds__(TXL_THREADS) void k_txlog_report(const MemberRef *M
 // ---------------------------------------------------------------------------------------------
 // host side
 
-struct reina_txlog {
-    reina_engine_t *e0 = nullptr;            // the engine, or the group's representative
-    reina_group *g = nullptr;                // a group's log
-    std::vector<reina_engine_t *> members;
-    const MemberRef *d_refs = nullptr;       // the engine's / the group's member table (device)
+struct reina_txlog : attachment {            // (last_day: the last day recorded)
     uint32_t *d_log = nullptr;               // [members][stride]
     size_t stride = 0;                       // words a member: n_agents rounded up to whole tiles
     bool by_hot = true;                      // k_txlog_day's form (REINA_TXLOG_FORM=log: the log word of every active agent; measurement handle)
-    int64_t last_day = -1;                   // the last day recorded
 };
 
 static void free_txlog(reina_txlog *l) {
@@ -282,71 +217,48 @@ static void free_txlog(reina_txlog *l) {
     delete l;
 }
 
-static uint32_t txlog_grid(const reina_txlog *l, uint32_t units) {
-    const uint32_t K = (uint32_t)l->members.size();
-    uint32_t per = 8u * l->e0->n_cus / K;   // workgroups a member
-    if (per < 1u) per = 1u;
-    return units < per ? (units ? units : 1u) : per;
-}
+// a launch that streams: eight workgroups a compute unit
+static uint32_t txlog_grid(const reina_txlog *l, uint32_t units) { return member_grid(l->e0->n_cus, (uint32_t)l->members.size(), units, 8u); }
 
 static int txlog_create(const std::vector<reina_engine_t *> &members, reina_group *g, const MemberRef *d_refs, hipStream_t s, reina_txlog_t **out) {
     if (!out) return REINA_E_INVALID;
-    for (auto m : members) {
-        if (!m->bound) return REINA_E_NOT_BOUND;
-        if (m->cfg.n_shards > 1 || m->exact || m->coll_fn || m->a2a_fn) {
-            g_last_error = "txlog: sharded engines are refused (links are global ids, and a shard sees only its own agents' onsets), exact attribution included";
-            return REINA_E_INVALID;
-        }
+    if (int rc = attachment_check_members(members, "txlog", "links are global ids, and a shard sees only its own agents' onsets")) return rc;
+    for (auto m : members)
         if (reinterpret_cast<uintptr_t>(m->buf.hot) & 15u) {
             g_last_error = "txlog: the hot words must be 16-byte aligned";
             return REINA_E_INVALID;
         }
-    }
-    reina_txlog *l = new reina_txlog();
-    l->e0 = members[0];
-    l->g = g;
-    l->members = members;
-    l->d_refs = d_refs;
+    std::unique_ptr<reina_txlog, void (*)(reina_txlog *)> l(new reina_txlog(), free_txlog);   // (freed by a failing return)
+    l->e0 = members[0], l->g = g, l->members = members, l->d_refs = d_refs;
     const char *form = std::getenv("REINA_TXLOG_FORM");
     l->by_hot = !(form && std::strcmp(form, "log") == 0);
     const uint32_t N = l->e0->cfg.n_agents, K = (uint32_t)members.size();
     l->stride = ((size_t)N + TXL_TILE - 1u) / TXL_TILE * TXL_TILE;
-    HIP_CHECK_OR(hipMalloc(&l->d_log, sizeof(uint32_t) * l->stride * K), free_txlog(l));
-    const uint32_t grid = txlog_grid(l, ((N + 3u) / 4u + TXL_THREADS - 1u) / TXL_THREADS);
-    if (g)
-        hipLaunchKernelGGL(k_txlog_begin<true>, dim3(grid, K), dim3(TXL_THREADS), 0, s, d_refs, l->e0->h_ref, l->d_log, l->stride, N);
-    else
-        hipLaunchKernelGGL(k_txlog_begin<false>, dim3(grid, 1), dim3(TXL_THREADS), 0, s, d_refs, l->e0->h_ref, l->d_log, l->stride, N);
-    HIP_CHECK_OR(hipGetLastError(), free_txlog(l));
-    *out = l;
+    HIP_CHECK(hipMalloc(&l->d_log, sizeof(uint32_t) * l->stride * K));
+    const uint32_t grid = txlog_grid(l.get(), ((N + 3u) / 4u + TXL_THREADS - 1u) / TXL_THREADS);
+    launch_members(k_txlog_begin, g, grid, K, TXL_THREADS, s, d_refs, l->e0->h_ref, l->d_log, l->stride, N);
+    *out = l.release();
     return REINA_OK;
 }
 
 // behind a day's last launch
 static int txlog_launch_day(reina_txlog *l, uint32_t day, hipStream_t s) {
-    if (day >= REINA_MAX_DAYS) {
-        g_last_error = "txlog: day >= REINA_MAX_DAYS (4096)";
-        return REINA_E_INVALID;
-    }
+    if (int rc = attachment_check_day(day)) return rc;
     const uint32_t N = l->e0->cfg.n_agents, K = (uint32_t)l->members.size();
     // (the hot-word tests hold for the days that follow a recorded day: the first day, and a day after a gap, read the log)
     const uint32_t by_hot = l->by_hot && l->last_day >= 0 && (int64_t)day == l->last_day + 1 ? 1u : 0u;
     const uint32_t tiles = (N + TXL_TILE - 1u) / TXL_TILE;
     const uint32_t grid = txlog_grid(l, (tiles + TXL_THREADS / 64u - 1u) / (TXL_THREADS / 64u));
-    if (l->g)
-        hipLaunchKernelGGL(k_txlog_day<true>, dim3(grid, K), dim3(TXL_THREADS), 0, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, N, day, by_hot);
-    else
-        hipLaunchKernelGGL(k_txlog_day<false>, dim3(grid, 1), dim3(TXL_THREADS), 0, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, N, day, by_hot);
-    HIP_CHECK(hipGetLastError());
+    launch_members(k_txlog_day, l->g, grid, K, TXL_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, N, day, by_hot);
     l->last_day = day;
     return REINA_OK;
 }
+static int txlog_after_day(attachment *a, const reina_day_t &d, hipStream_t s) { return txlog_launch_day(static_cast<reina_txlog *>(a), d.day, s); }
 
 static int txlog_report(reina_txlog *l, const uint8_t *age_group, uint32_t n_groups, uint32_t n_days, uint64_t *dev_report, hipStream_t s) {
-    if (!age_group || n_groups < 1u || n_groups > REINA_TXLOG_MAX_GROUPS) {
-        g_last_error = "txlog report: age_group must be a table of groups, 1 <= n_groups <= REINA_TXLOG_MAX_GROUPS";
-        return REINA_E_INVALID;
-    }
+    TxlArgs a;
+    if (int rc = age_group_args(l->e0, age_group, n_groups, REINA_TXLOG_MAX_GROUPS, "txlog report", &a.p)) return rc;
+    a.n_days = n_days;
     if (n_days < 1u || n_days > REINA_MAX_DAYS) {
         g_last_error = "txlog report: n_days must be in [1, REINA_MAX_DAYS]";
         return REINA_E_INVALID;
@@ -355,42 +267,13 @@ static int txlog_report(reina_txlog *l, const uint8_t *age_group, uint32_t n_gro
         g_last_error = "txlog report: the report must be a 16-byte aligned device buffer";
         return REINA_E_INVALID;
     }
-    const reina_engine_t *e = l->e0;
-    TxlArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.n_agents = e->cfg.n_agents;
-    a.nr_ages = e->cfg.nr_ages;
-    a.n_days = n_days;
-    std::memcpy(a.age_start, e->cfg.age_start, sizeof(a.age_start));
-    for (uint32_t k = 0; k < e->cfg.nr_ages; k++) {
-        if (age_group[k] >= n_groups) {
-            g_last_error = "txlog report: an age's group is not below n_groups";
-            return REINA_E_INVALID;
-        }
-        a.group[k] = age_group[k];
-    }
     const uint32_t K = (uint32_t)l->members.size();
     const size_t block = REINA_TXLOG_REPORT_WORDS(n_days) * 8u;
     HIP_CHECK(hipMemsetAsync(dev_report, 0, block * K, s));
     HIP_CHECK(hipMemset2DAsync(dev_report + REINA_TXLOG_SCALARS + REINA_TXLOG_S_FIRST_DAY, block, 0xFF, 8u, K, s));
-    const uint32_t tiles = (a.n_agents + TXL_TILE - 1u) / TXL_TILE;
-    uint32_t per = 4u * e->n_cus / K;   // workgroups a member (each flushes its LDS tables once)
-    if (per < 1u) per = 1u;
-    const uint32_t grid = tiles < per ? (tiles ? tiles : 1u) : per;
-    if (l->g)
-        hipLaunchKernelGGL(k_txlog_report<true>, dim3(grid, K), dim3(TXL_THREADS), 0, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, dev_report, a);
-    else
-        hipLaunchKernelGGL(k_txlog_report<false>, dim3(grid, 1), dim3(TXL_THREADS), 0, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, dev_report, a);
-    HIP_CHECK(hipGetLastError());
-    return REINA_OK;
-}
-
-static int txlog_kind(const reina_txlog *l, bool group, const char *what) {
-    if (!l) return REINA_E_INVALID;
-    if ((l->g != nullptr) != group) {
-        g_last_error = std::string(what) + (group ? ": the log was made for one engine -- use the entry point without group_" : ": the log was made for a group -- use the reina_group_txlog_ entry point");
-        return REINA_E_INVALID;
-    }
+    // (four workgroups a compute unit: each flushes its LDS tables once)
+    const uint32_t grid = member_grid(l->e0->n_cus, K, (a.p.n_agents + TXL_TILE - 1u) / TXL_TILE, 4u);
+    launch_members(k_txlog_report, l->g, grid, K, TXL_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, dev_report, a);
     return REINA_OK;
 }
 
@@ -422,39 +305,25 @@ int reina_txlog_record_day(reina_txlog_t *log, uint32_t day, void *stream) {
 
 int reina_txlog_run_days(reina_txlog_t *log, const reina_day_t *days, uint32_t n_days, int32_t *history_base, void *stream) {
     if (!days) return REINA_E_INVALID;
-    if (int rc = txlog_kind(log, false, "reina_txlog_run_days")) return rc;
-    // (always the three-launch day: reina_step_day, never the several-days-in-one-launch form)
-    for (uint32_t k = 0; k < n_days; k++) {
-        reina_day_t d = days[k];
-        d.history_row = history_base ? history_base + (size_t)k * REINA_COUNTER_WORDS : nullptr;
-        if (d.day >= REINA_MAX_DAYS) {
-            g_last_error = "txlog: day >= REINA_MAX_DAYS (4096)";
-            return REINA_E_INVALID;
-        }
-        if (int rc = reina_step_day(log->e0, &d, stream)) return rc;
-        if (int rc = txlog_launch_day(log, d.day, (hipStream_t)stream)) return rc;
-    }
-    return REINA_OK;
+    if (int rc = attachment_kind(log, false, "reina_txlog_run_days")) return rc;
+    return engine_run_days(log->e0, days, n_days, history_base, stream, day_hooks{log, nullptr, txlog_after_day});
 }
 
 int reina_group_txlog_run_days(reina_txlog_t *log, const reina_day_t *days, uint32_t n_days, int32_t *const *history_bases, void *stream) {
     if (!days) return REINA_E_INVALID;
-    if (int rc = txlog_kind(log, true, "reina_group_txlog_run_days")) return rc;
-    for (uint32_t k = 0; k < n_days; k++)
-        if (days[k].day >= REINA_MAX_DAYS) {
-            g_last_error = "txlog: day >= REINA_MAX_DAYS (4096)";
-            return REINA_E_INVALID;
-        }
-    return group_run_days(log->g, days, n_days, history_bases, stream, nullptr, log);
+    if (int rc = attachment_kind(log, true, "reina_group_txlog_run_days")) return rc;
+    for (uint32_t k = 0; k < n_days; k++)   // (before any day runs: the record launch comes behind its day)
+        if (int rc = attachment_check_day(days[k].day)) return rc;
+    return group_run_days(log->g, days, n_days, history_bases, stream, day_hooks{log, nullptr, txlog_after_day});
 }
 
 int reina_txlog_report(reina_txlog_t *log, const uint8_t *age_group, uint32_t n_groups, uint32_t n_days, uint64_t *dev_report, void *stream) {
-    if (int rc = txlog_kind(log, false, "reina_txlog_report")) return rc;
+    if (int rc = attachment_kind(log, false, "reina_txlog_report")) return rc;
     return txlog_report(log, age_group, n_groups, n_days, dev_report, (hipStream_t)stream);
 }
 
 int reina_group_txlog_report(reina_txlog_t *log, const uint8_t *age_group, uint32_t n_groups, uint32_t n_days, uint64_t *dev_report, void *stream) {
-    if (int rc = txlog_kind(log, true, "reina_group_txlog_report")) return rc;
+    if (int rc = attachment_kind(log, true, "reina_group_txlog_report")) return rc;
     return txlog_report(log, age_group, n_groups, n_days, dev_report, (hipStream_t)stream);
 }
 

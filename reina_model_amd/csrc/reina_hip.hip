@@ -33,6 +33,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -1292,13 +1293,17 @@ int reina_group_upload_contact_tables(reina_group_t *g, const reina_contact_tabl
     return REINA_OK;
 }
 
-// a policy's launch ahead of a day's opening (k_policy.inc)
-static int policy_launch_day(struct reina_policy *p, const reina_day_t &dp, hipStream_t s);
-// a transmission log's launch behind a day's last one (k_txlog.inc)
-static int txlog_launch_day(struct reina_txlog *l, uint32_t day, hipStream_t s);
+// what an attachment (k_addons.inc) queues around every day of a run: `before` ahead of the day's opening launch (a policy),
+// `after` behind its last one (a transmission log)
+struct attachment;
+struct day_hooks {
+    attachment *a = nullptr;
+    int (*before)(attachment *a, const reina_day_t &d, hipStream_t s) = nullptr;
+    int (*after)(attachment *a, const reina_day_t &d, hipStream_t s) = nullptr;
+};
 
 static int group_run_days(reina_group_t *g, const reina_day_t *days, uint32_t n_days, int32_t *const *history_bases,
-                          void *stream, struct reina_policy *policy, struct reina_txlog *txlog = nullptr) {
+                          void *stream, const day_hooks &hooks = day_hooks()) {
     if (!g || !days) return REINA_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const uint32_t K = (uint32_t)g->members.size();
@@ -1320,10 +1325,10 @@ static int group_run_days(reina_group_t *g, const reina_day_t *days, uint32_t n_
     for (uint32_t d = 0; d < n_days; d++) {
         reina_day_t dp = days[d];
         dp.history_row = nullptr;
-        int rc = policy ? policy_launch_day(policy, dp, s) : REINA_OK;
+        int rc = hooks.before ? hooks.before(hooks.a, dp, s) : REINA_OK;
         if (rc == REINA_OK) rc = launch_day_begin(e0, g->d_refs, K, dp, d, s);
         if (rc == REINA_OK) rc = launch_day_end(e0, g->d_refs, K, dp, s);
-        if (rc == REINA_OK && txlog) rc = txlog_launch_day(txlog, dp.day, s);
+        if (rc == REINA_OK && hooks.after) rc = hooks.after(hooks.a, dp, s);
         if (rc) {
             e0->h_ref = own_ref;
             return rc;
@@ -1339,7 +1344,7 @@ static int group_run_days(reina_group_t *g, const reina_day_t *days, uint32_t n_
 
 int reina_group_run_days(reina_group_t *g, const reina_day_t *days, uint32_t n_days, int32_t *const *history_bases,
                          void *stream) {
-    return group_run_days(g, days, n_days, history_bases, stream, nullptr);
+    return group_run_days(g, days, n_days, history_bases, stream);
 }
 
 int reina_read_counters(reina_engine_t *e, int32_t *out_host, void *stream) {
@@ -1429,6 +1434,9 @@ int reina_profile_read(reina_engine_t *e, double *scan_ms_total, uint64_t *scan_
 }
 
 }  // extern "C"
+
+// what the parts below share: wave helpers, link classification, launch geometry, the attachment base
+#include "k_addons.inc"
 
 // snapshots of an engine between days (include/reina_snapshot.h): kernels and entry points
 #include "k_snapshot.inc"

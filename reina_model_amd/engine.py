@@ -245,6 +245,31 @@ class EngineError(RuntimeError):
     pass
 
 
+def bind_optional_abi(lib, prefix, functions, argtypes, version_name, version):
+    """The entry points `functions` of one of the headers beside reina_hip.h, typed by `argtypes` (name -> list; none for
+    the version function), or None when the library lacks one of them (a library of the day ABI only)."""
+    if not all(hasattr(lib, prefix + n) for n in functions):
+        return None
+    f = {n: getattr(lib, prefix + n) for n in functions}
+    for n in functions:
+        f[n].argtypes = argtypes.get(n, [])
+        f[n].restype = ctypes.c_int
+    if f[version_name]() != version:
+        raise EngineError('%s%s() = %d, this binding is written for %d' % (prefix, version_name, f[version_name](), version))
+    return f
+
+
+def is_device(engine):
+    """the engine's state lives on a GPU (engine.alloc is a TorchAllocator), not in the CPU checker's numpy arrays"""
+    return getattr(engine.alloc, 'torch', None) is not None
+
+
+def mark_stale(engines):
+    """something was launched on these engines behind their backs: a prefetched counter block no longer holds"""
+    for e in engines:
+        e._prefetched = False
+
+
 class NumpyAllocator:
     """Host-memory allocator (used by the test-suite to drive a CPU implementation of the ABI)."""
     device = 'cpu'
@@ -568,8 +593,7 @@ class EngineGroup:
         hp = None
         if history_ptrs is not None:
             hp = (ctypes.c_void_p * len(self.engines))(*[int(p) for p in history_ptrs])
-        for e in self.engines:
-            e._prefetched = False
+        mark_stale(self.engines)
         self.engines[0]._check(self.f['group_run_days'](self._h, arr, n, hp, self.alloc.stream()), 'group_run_days')
 
 

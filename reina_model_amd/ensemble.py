@@ -323,7 +323,7 @@ def transmission_reports(contexts, age_groups=None, group=None):
     for c in contexts:
         c._check_tx_capable()
     table, labels = contexts[0]._tx_groups(age_groups)
-    if getattr(contexts[0].engine.alloc, 'torch', None) is None:
+    if not _eng.is_device(contexts[0].engine):
         reps = [_tx.report_engine(c.engine, table, len(labels)) for c in contexts]
     else:
         own_group = group is None

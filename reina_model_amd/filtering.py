@@ -37,16 +37,8 @@ STREAMS = {'all_detected': ('all_detected', True), 'dead': ('dead', True),
 
 def bind_filter_abi(lib, prefix):
     """The particle-filter entry points of a library, or None when it has none."""
-    if not all(hasattr(lib, prefix + n) for n in FILTER_FUNCTIONS):
-        return None
-    f = {n: getattr(lib, prefix + n) for n in FILTER_FUNCTIONS}
-    f['filter_version'].argtypes = []
-    f['group_clone'].argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
-    for n in FILTER_FUNCTIONS:
-        f[n].restype = ctypes.c_int
-    if f['filter_version']() != FILTER_VERSION:
-        raise _eng.EngineError('%sfilter_version() = %d, this binding is written for %d' % (prefix, f['filter_version'](), FILTER_VERSION))
-    return f
+    argtypes = {'group_clone': [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]}
+    return _eng.bind_optional_abi(lib, prefix, FILTER_FUNCTIONS, argtypes, 'filter_version', FILTER_VERSION)
 
 
 # ------------------------------------------------------------------------------------------------ the clone
@@ -111,7 +103,7 @@ def clone_group(group, pairs):
     device (reina_group_clone), clone_state per pair for host-memory engines."""
     engines = group.engines
     e0 = engines[0]
-    if getattr(e0.alloc, 'torch', None) is None:
+    if not _eng.is_device(e0):
         p = check_pairs(pairs, len(engines))
         mq = min(e.config.max_queue for e in engines)
         for d, s in p:
@@ -124,8 +116,7 @@ def clone_group(group, pairs):
     if len(flat) % 2:
         raise ValueError('clone: pairs are (dst, src)')
     arr = (ctypes.c_uint32 * max(len(flat), 1))(*[x & 0xFFFFFFFF for x in flat])
-    for e in engines:
-        e._prefetched = False
+    _eng.mark_stale(engines)
     e0._check(f['group_clone'](group._h, arr, len(flat) // 2, e0.alloc.stream()), 'group_clone')
 
 

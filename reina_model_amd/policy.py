@@ -56,27 +56,18 @@ class RuleABI(ctypes.Structure):
                 ('n_days', ctypes.c_uint32), ('review_every', ctypes.c_uint32), ('min_days', ctypes.c_uint32),
                 ('start_day', ctypes.c_uint32), ('reserved_', ctypes.c_uint32),
                 ('up', ctypes.c_int32 * MAX_LEVELS), ('down', ctypes.c_int32 * MAX_LEVELS)]
+_vp, _u32 = ctypes.c_void_p, ctypes.c_uint32
+_POLICY_ARGTYPES = {'policy_create': [_vp, ctypes.POINTER(RuleABI), ctypes.POINTER(_vp)],
+                    'group_policy_create': [_vp, ctypes.POINTER(RuleABI), ctypes.POINTER(_vp)],
+                    'policy_destroy': [_vp], 'policy_upload_level': [_vp, _u32, ctypes.POINTER(_eng.ContactTablesABI), _vp],
+                    'policy_run_days': [_vp, ctypes.POINTER(_eng.Day), _u32, _vp, _vp],
+                    'group_policy_run_days': [_vp, ctypes.POINTER(_eng.Day), _u32, ctypes.POINTER(_vp), _vp],
+                    'policy_read_trace': [_vp, _u32, _u32, _vp, _vp]}
 
 
 def bind_policy_abi(lib, prefix):
     """The policy entry points of a library, or None when it has none (the CPU checker's)."""
-    if not all(hasattr(lib, prefix + n) for n in POLICY_FUNCTIONS):
-        return None
-    f = {n: getattr(lib, prefix + n) for n in POLICY_FUNCTIONS}
-    vp = ctypes.c_void_p
-    f['policy_version'].argtypes = []
-    f['policy_create'].argtypes = [vp, ctypes.POINTER(RuleABI), ctypes.POINTER(vp)]
-    f['group_policy_create'].argtypes = [vp, ctypes.POINTER(RuleABI), ctypes.POINTER(vp)]
-    f['policy_destroy'].argtypes = [vp]
-    f['policy_upload_level'].argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(_eng.ContactTablesABI), vp]
-    f['policy_run_days'].argtypes = [vp, ctypes.POINTER(_eng.Day), ctypes.c_uint32, vp, vp]
-    f['group_policy_run_days'].argtypes = [vp, ctypes.POINTER(_eng.Day), ctypes.c_uint32, ctypes.POINTER(vp), vp]
-    f['policy_read_trace'].argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
-    for n in POLICY_FUNCTIONS:
-        f[n].restype = ctypes.c_int
-    if f['policy_version']() != POLICY_VERSION:
-        raise _eng.EngineError('%spolicy_version() = %d, this binding is written for %d' % (prefix, f['policy_version'](), POLICY_VERSION))
-    return f
+    return _eng.bind_optional_abi(lib, prefix, POLICY_FUNCTIONS, _POLICY_ARGTYPES, 'policy_version', POLICY_VERSION)
 
 
 class Signal:
@@ -368,8 +359,7 @@ class DevicePolicy:
     def run_day_array(self, arr, n, history):
         """history: a device pointer (one engine) or one per member (a group), or None"""
         if self._grouped:
-            for e in self.group.engines:
-                e._prefetched = False
+            _eng.mark_stale(self.group.engines)
             hp = None
             if history is not None:
                 hp = (ctypes.c_void_p * self.members)(*[int(p) for p in history])

@@ -34,24 +34,14 @@ FILE_MAGIC = b'RSNPFILE'
 HOST_STATE_FORMAT = 1
 
 SNAPSHOT_FUNCTIONS = ('snapshot_version', 'snap_measure', 'snap_pack', 'snap_unpack', 'group_snap_unpack')
+_vp = ctypes.c_void_p
+_SNAPSHOT_ARGTYPES = {'snap_measure': [_vp, ctypes.POINTER(ctypes.c_uint64), _vp], 'snap_pack': [_vp, _vp, ctypes.c_uint64, _vp],
+                      'snap_unpack': [_vp, _vp, _vp], 'group_snap_unpack': [_vp, _vp, _vp]}
 
 
 def bind_snapshot_abi(lib, prefix):
     """The snapshot entry points of a library, or None when it has none (a library of the day ABI only)."""
-    if not all(hasattr(lib, prefix + n) for n in SNAPSHOT_FUNCTIONS):
-        return None
-    f = {n: getattr(lib, prefix + n) for n in SNAPSHOT_FUNCTIONS}
-    vp = ctypes.c_void_p
-    f['snapshot_version'].argtypes = []
-    f['snap_measure'].argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), vp]
-    f['snap_pack'].argtypes = [vp, vp, ctypes.c_uint64, vp]
-    f['snap_unpack'].argtypes = [vp, vp, vp]
-    f['group_snap_unpack'].argtypes = [vp, vp, vp]
-    for n in SNAPSHOT_FUNCTIONS:
-        f[n].restype = ctypes.c_int
-    if f['snapshot_version']() != SNAPSHOT_VERSION:
-        raise _eng.EngineError('%ssnapshot_version() = %d, this binding is written for %d' % (prefix, f['snapshot_version'](), SNAPSHOT_VERSION))
-    return f
+    return _eng.bind_optional_abi(lib, prefix, SNAPSHOT_FUNCTIONS, _SNAPSHOT_ARGTYPES, 'snapshot_version', SNAPSHOT_VERSION)
 
 
 def fnv1a64(data):
@@ -198,10 +188,6 @@ def unpack_numpy(engine, disease, image):
     return h
 
 
-def _is_device(engine):
-    return getattr(engine.alloc, 'torch', None) is not None
-
-
 def _snap_f(engine):
     f = getattr(engine, 'snap_f', None)
     if f is None:
@@ -211,7 +197,7 @@ def _snap_f(engine):
 
 def pack_engine(engine, disease, testing_ever):
     """The engine's image: packed by the library's kernels into a device tensor (HIP engine), by pack_numpy otherwise."""
-    if not _is_device(engine):
+    if not _eng.is_device(engine):
         return pack_numpy(engine, disease, testing_ever)
     f = _snap_f(engine)
     torch = engine.alloc.torch
@@ -246,7 +232,7 @@ def _check_image_length(dev):
 
 def unpack_engine(engine, disease, image):
     """Restore `image` (host or device) into one engine."""
-    if not _is_device(engine):
+    if not _eng.is_device(engine):
         return unpack_numpy(engine, disease, _host_image(image))
     f = _snap_f(engine)
     dev = _device_image(engine.alloc, image)
@@ -260,7 +246,7 @@ def unpack_group(group, disease, image):
     """Restore `image` into every member of an engine group: ONE launch on the device (reina_group_snap_unpack), the numpy
     unpacker per member for host-memory engines."""
     e0 = group.engines[0]
-    if not _is_device(e0):
+    if not _eng.is_device(e0):
         for e in group.engines:
             unpack_numpy(e, disease, _host_image(image))
         return
@@ -268,8 +254,8 @@ def unpack_group(group, disease, image):
     dev = _device_image(e0.alloc, image)
     _check_image_length(dev)
     e0._check(f['group_snap_unpack'](group._h, dev.data_ptr(), e0.alloc.stream()), 'group_snap_unpack')
+    _eng.mark_stale(group.engines)
     for e in group.engines:
-        e._prefetched = False
         e._keep_image = dev
 
 

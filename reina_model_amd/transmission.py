@@ -57,18 +57,9 @@ def rounds_for(max_depth):
 
 def bind_tx_abi(lib, prefix):
     """The transmission-report entry points of a library, or None when it has none."""
-    if not all(hasattr(lib, prefix + n) for n in TX_FUNCTIONS):
-        return None
-    f = {n: getattr(lib, prefix + n) for n in TX_FUNCTIONS}
     vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    f['tx_version'].argtypes = []
-    f['tx_report'].argtypes = [vp, vp, u32, u32, vp, vp, vp]
-    f['group_tx_report'].argtypes = [vp, vp, u32, u32, vp, vp, vp]
-    for n in TX_FUNCTIONS:
-        f[n].restype = ctypes.c_int
-    if f['tx_version']() != TX_VERSION:
-        raise _eng.EngineError('%stx_version() = %d, this binding is written for %d' % (prefix, f['tx_version'](), TX_VERSION))
-    return f
+    argtypes = {'tx_report': [vp, vp, u32, u32, vp, vp, vp], 'group_tx_report': [vp, vp, u32, u32, vp, vp, vp]}
+    return _eng.bind_optional_abi(lib, prefix, TX_FUNCTIONS, argtypes, 'tx_version', TX_VERSION)
 
 
 def default_age_groups(nr_ages):
@@ -190,10 +181,6 @@ def _day_depth(counters):
     return min(max(day, 0), _eng.MAX_DAYS) + 1
 
 
-def _is_device(engine):
-    return getattr(engine.alloc, 'torch', None) is not None
-
-
 def _tx_f(engine):
     f = getattr(engine, 'tx_f', None)
     if f is None:
@@ -225,7 +212,7 @@ def report_engine(engine, age_group, n_groups=None):
     nr_ages = engine.config.nr_ages
     table, ng = _group_table(age_group, nr_ages)
     ng = max(ng, int(n_groups or 0))
-    if not _is_device(engine):
+    if not _eng.is_device(engine):
         hot, inf, cnt, counters = _host_fields(engine)
         age_start = np.asarray(engine.config.age_start, dtype=np.int64)
         r = report_numpy(hot, inf, cnt, age_start, table[:nr_ages], _day_depth(counters))
@@ -243,7 +230,7 @@ def report_group(group, age_group, n_groups=None):
     """The reports of every member of an engine group: one launch per pass on the device, report_engine per member
     otherwise."""
     e0 = group.engines[0]
-    if not _is_device(e0):
+    if not _eng.is_device(e0):
         return [report_engine(e, age_group, n_groups) for e in group.engines]
     for e in group.engines:
         _check_unsharded(e.config)
@@ -257,8 +244,7 @@ def report_group(group, age_group, n_groups=None):
     ptrs = (ctypes.c_void_p * K)(*[s.data_ptr() for s in scratch])
     rep = torch.empty(K * REPORT_WORDS, dtype=torch.int64, device=dev)
     e0._check(f['group_tx_report'](group._h, table.ctypes.data, ng, 0, ptrs, rep.data_ptr(), e0.alloc.stream()), 'group_tx_report')
-    for e in group.engines:
-        e._prefetched = False
+    _eng.mark_stale(group.engines)
     del scratch
     words = rep.cpu().numpy().view(np.uint64).reshape(K, REPORT_WORDS)
     out = []

@@ -28,6 +28,7 @@ import ctypes
 import numpy as np
 
 from . import engine as _eng
+from .transmission import _group_table
 
 TXLOG_VERSION = 1              # include/reina_txlog.h: REINA_TXLOG_VERSION
 NONE, BEFORE = 0xFFFF, 0xFFFE
@@ -67,30 +68,17 @@ def cohort_offset(n_days):
 def report_words(n_days):
     """include/reina_txlog.h: REINA_TXLOG_REPORT_WORDS"""
     return FIXED_WORDS + int(n_days) * DAY_WORDS
+_vp, _u32 = ctypes.c_void_p, ctypes.c_uint32
+_TXLOG_ARGTYPES = {'txlog_create': [_vp, _vp, _vp], 'group_txlog_create': [_vp, _vp, _vp], 'txlog_destroy': [_vp],
+                   'txlog_record_day': [_vp, _u32, _vp],
+                   'txlog_run_days': [_vp, _vp, _u32, _vp, _vp], 'group_txlog_run_days': [_vp, _vp, _u32, _vp, _vp],
+                   'txlog_report': [_vp, _vp, _u32, _u32, _vp, _vp], 'group_txlog_report': [_vp, _vp, _u32, _u32, _vp, _vp],
+                   'txlog_read': [_vp, _u32, _vp, _vp], 'txlog_write': [_vp, _u32, _vp, _vp]}
 
 
 def bind_txlog_abi(lib, prefix):
     """The log's entry points of a library, or None when it has none."""
-    if not all(hasattr(lib, prefix + n) for n in TXLOG_FUNCTIONS):
-        return None
-    f = {n: getattr(lib, prefix + n) for n in TXLOG_FUNCTIONS}
-    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    f['txlog_version'].argtypes = []
-    f['txlog_create'].argtypes = [vp, vp, vp]
-    f['group_txlog_create'].argtypes = [vp, vp, vp]
-    f['txlog_destroy'].argtypes = [vp]
-    f['txlog_record_day'].argtypes = [vp, u32, vp]
-    f['txlog_run_days'].argtypes = [vp, vp, u32, vp, vp]
-    f['group_txlog_run_days'].argtypes = [vp, vp, u32, vp, vp]
-    f['txlog_report'].argtypes = [vp, vp, u32, u32, vp, vp]
-    f['group_txlog_report'].argtypes = [vp, vp, u32, u32, vp, vp]
-    f['txlog_read'].argtypes = [vp, u32, vp, vp]
-    f['txlog_write'].argtypes = [vp, u32, vp, vp]
-    for n in TXLOG_FUNCTIONS:
-        f[n].restype = ctypes.c_int
-    if f['txlog_version']() != TXLOG_VERSION:
-        raise _eng.EngineError('%stxlog_version() = %d, this binding is written for %d' % (prefix, f['txlog_version'](), TXLOG_VERSION))
-    return f
+    return _eng.bind_optional_abi(lib, prefix, TXLOG_FUNCTIONS, _TXLOG_ARGTYPES, 'txlog_version', TXLOG_VERSION)
 
 
 # ------------------------------------------------------------------------------------------------ the specification
@@ -114,11 +102,6 @@ def record_numpy(log, hot, day):
     inf = np.where((inf == NONE) & (st != 0), day, inf).astype(np.uint32)
     ons = np.where((ons == NONE) & (st >= S_ILLNESS), day, ons).astype(np.uint32)
     return ons << 16 | inf
-
-
-def _group_table(age_group, nr_ages):
-    from .transmission import _group_table as g
-    return g(age_group, nr_ages)
 
 
 def report_numpy(hot, infector, n_infected, log, age_start, age_group, n_days):
@@ -305,10 +288,6 @@ class LogReport:
 
 # ------------------------------------------------------------------------------------------------ logs
 
-def _is_device(engine):
-    return getattr(engine.alloc, 'torch', None) is not None
-
-
 def check_capable(ctx):
     if ctx.n_shards != 1 or ctx.always_collective:
         raise ValueError('transmission log: sharded Contexts are refused (links are global ids, and a shard sees only its own '
@@ -348,8 +327,7 @@ class DeviceLog:
             pass
 
     def _touch(self):
-        for e in ([self.engine] if self.group is None else self.group.engines):
-            e._prefetched = False
+        _eng.mark_stale([self.engine] if self.group is None else self.group.engines)
 
     def record_day(self, day):
         self.engine._check(self.f['txlog_record_day'](self._h, int(day), self.engine.alloc.stream()), 'txlog_record_day')
@@ -397,7 +375,7 @@ class TransmissionLog:
         self.begin_day = int(ctx.day)
         self.device, self._words = device, None
         if device is None:
-            if not host and _is_device(ctx.engine) and ctx.engine.txlog_f is not None:
+            if not host and _eng.is_device(ctx.engine) and ctx.engine.txlog_f is not None:
                 self.device = DeviceLog(ctx.engine)
             else:
                 self._words = begin_numpy(_host_array(ctx.engine.tensors['hot']))

@@ -8,6 +8,8 @@ import pytest
 import par_backend
 import snap_util
 import tx_util
+import txlog_util
+from filter_util import small_scenario
 from golden_util import load_run, variables_for
 from reina_model_amd import datasets, ensemble, simulation, transmission as tx
 from reina_model_amd import engine as eng
@@ -105,6 +107,17 @@ def test_hus_day_200_invariants():
     assert int(r.offspring_sum[:, 1].sum()) == int(hist[1:, base + eng.S_TOTAL_INFECTIONS].sum()) + int(final[base + eng.S_TOTAL_INFECTIONS])
     hot, inf, cnt, day = _host_state(ctx)
     _assert_same(r, _spec_like_engine(hot, inf, cnt, np.asarray(ctx.engine.config.age_start), ctx.age_group_indices[:ctx.nr_ages], day, len(hot)))
+
+
+def test_tree_report_and_log_report_classify_links_alike():
+    # one simulated state through k_tx_links and k_txlog_report (the specifications' twin: tests/test_txlog.py)
+    v, ages = small_scenario()
+    ctx = simulation.make_context(v, age_counts=ages, seed=3, txlog=True)
+    ctx.run(60)
+    assert ctx.transmission_log.on_device
+    tree, log = ctx.transmission_report(), ctx.transmission_log.report()
+    txlog_util.assert_same_links(tree, log)
+    assert tree.n_linked > 0 and tree.n_roots > 0
 
 
 def test_group_report_equals_single_reports():

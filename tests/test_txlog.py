@@ -14,7 +14,7 @@ import tx_util
 import txlog_util as tu
 from filter_util import small_scenario
 from reina_model_amd import engine as eng
-from reina_model_amd import simulation, txlog as txl
+from reina_model_amd import simulation, transmission as tx, txlog as txl
 from reina_model_amd.variables import VARIABLE_DEFAULTS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -73,6 +73,18 @@ def test_empty_state_and_report_accessors():
     assert list(rc.columns) == ['r_c', 'cohort', 'closed_share'] and int(rc['cohort'].sum()) == int(r.cohort[..., 0].sum())
     day = int(np.flatnonzero(r.cohort[..., 0].sum(axis=1))[0])
     assert rc['r_c'].iloc[day] == r.cohort[day, :, 1].sum() / r.cohort[day, :, 0].sum()
+
+
+@pytest.mark.parametrize('pattern', tx_util.PATTERNS)
+def test_tree_report_and_log_report_classify_links_alike(pattern):
+    # the two specifications on one state (the device twin: tests/test_transmission_gpu.py)
+    n = 513
+    hot, inf, cnt, log = tu.forest_state(n, pattern)
+    age_start, g = tx_util.age_start_of(n), tx_util.groups()
+    tree = tx.report_numpy(hot, inf, cnt, age_start, g, n)
+    tu.assert_same_links(tree, txl.report_numpy(hot, inf, cnt, log, age_start, g, tu.N_DAYS))
+    if pattern == 'bad_links':
+        assert tree.bad_links > 0 and tree.n_linked > 0 and tree.n_roots > 0
 
 
 # ---------------------------------------------------------------------------------------------- 2. record_numpy

@@ -77,6 +77,17 @@ def combos_state():
     return hot, inf, cnt, log
 
 
+def assert_same_links(tree, log):
+    """a TransmissionReport and a LogReport of ONE state classify its agents alike: infected, roots, links, bad links, and the
+    links of every variant (the age matrix summed over its groups == the link phases summed)"""
+    assert tree.n_infected_agents == log.infected
+    assert tree.n_roots == log.infected - log.links - log.bad_links
+    assert tree.n_linked == log.links
+    assert tree.bad_links == log.bad_links
+    got, want = tree.matrix.sum(axis=(1, 2)), log.link_phase.sum(axis=1)
+    assert [int(x) for x in got] == [int(x) for x in want]
+
+
 def walk_report(hot, infector, n_infected, log, age_start, age_group, n_days):
     """Every field of a report, counted agent by agent in plain Python (independent of report_numpy)"""
     n = len(hot)
