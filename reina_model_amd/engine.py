@@ -270,6 +270,15 @@ def mark_stale(engines):
         e._prefetched = False
 
 
+def member_pointers(engines, history):
+    """What the group forms of run_day_array hand the library: `history` (one device pointer per member, or None) as a C array;
+    the members' prefetched counter blocks are stale from here on."""
+    mark_stale(engines)
+    if history is None:
+        return None
+    return (ctypes.c_void_p * len(engines))(*[int(p) for p in history])
+
+
 class NumpyAllocator:
     """Host-memory allocator (used by the test-suite to drive a CPU implementation of the ABI)."""
     device = 'cpu'
@@ -590,10 +599,7 @@ class EngineGroup:
 
     def run_day_array(self, arr, n, history_ptrs):
         """history_ptrs: one device pointer per member (row k of member m at ptr[m] + k rows) or None."""
-        hp = None
-        if history_ptrs is not None:
-            hp = (ctypes.c_void_p * len(self.engines))(*[int(p) for p in history_ptrs])
-        mark_stale(self.engines)
+        hp = member_pointers(self.engines, history_ptrs)
         self.engines[0]._check(self.f['group_run_days'](self._h, arr, n, hp, self.alloc.stream()), 'group_run_days')
 
 

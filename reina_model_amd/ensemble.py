@@ -21,6 +21,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import simulation
+from .dayrun import History, replay_plan
 from .filtering import particle_filter  # noqa: F401  (conditioned ensembles: reina_model_amd/filtering.py)
 
 
@@ -86,43 +87,39 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
         for m, c in enumerate(contexts):
             c.transmission_log = _txl.TransmissionLog(c, device=glog, member=m)
     a = group.alloc
-    days = plan['days']
-    K = len(contexts)
-    hist = a.zeros(K * days * _eng.COUNTER_WORDS, np.int32) if record_history else None
-    row = 4 * _eng.COUNTER_WORDS
-    done = 0
+    days, start_day = plan['days'], plan['start_day']
+    hist = History(days, record_history, group=group)
     dev = _pol.DevicePolicy(policy, contexts[0].start_date, group=group) if policy is not None else None
-    for si, (tables, arr, n) in enumerate(plan['segments']):
-        if dev is not None:
-            dev.upload_bank(plan['policy_banks'][si][0])
-            dev.run_day_array(arr, n, [a.ptr(hist) + row * (m * days + done) for m in range(K)] if record_history else None)
-            done += n
-            continue
-        if member_plans is not None:
-            for c, mp in zip(contexts, member_plans):
-                if mp['segments'][si][0] is not None:
-                    c.engine.upload_contact_tables(*mp['segments'][si][0])
-        elif tables is not None:
+
+    def upload_bank(si, tables):
+        dev.upload_bank(plan['policy_banks'][si][0])
+
+    def upload_member_tables(si, tables):   # (a sweep: every member its own)
+        for c, mp in zip(contexts, member_plans):
+            if mp['segments'][si][0] is not None:
+                c.engine.upload_contact_tables(*mp['segments'][si][0])
+
+    def upload_group_tables(si, tables):
+        if tables is not None:
             group.upload_contact_tables(*tables)
-        ptrs = [a.ptr(hist) + row * (m * days + done) for m in range(K)] if record_history else None
-        (glog if glog is not None else group).run_day_array(arr, n, ptrs)
-        done += n
+
+    if dev is not None:
+        replay_plan(plan, dev, hist, upload_bank)
+    else:
+        replay_plan(plan, glog if glog is not None else group, hist,
+                    upload_member_tables if member_plans is not None else upload_group_tables)
     _t('issued')
     if dev is not None:
-        trace = dev.read_trace(plan['start_day'], days)   # (the run's wait; the members' host-side table mirrors follow their levels)
+        trace = dev.read_trace(start_day, days)   # (the run's wait; the members' host-side table mirrors follow their levels)
         dev.close()
         seg_of_day, factors = _pol.plan_segments_of_days(plan), [b[1] for b in plan['policy_banks']]
     for m, c in enumerate(contexts):
         if dev is not None:
-            c.day = plan['start_day']
-            first_value = _pol._first_mobility(c, plan['mobility_history'][0]) if days else 0.0
-            _pol._finish(c, first_value, trace[m, :, 0], seg_of_day, factors, plan['start_day'] + days)
+            _pol._end_device_run(c, trace, m, start_day, plan['mobility_history'][0] if days else 0.0, seg_of_day, factors)
         else:
             c.mobility_history = (member_plans[m] if member_plans is not None else plan)['mobility_history']
-        c.day = plan['start_day'] + days
-    out = None
-    if record_history:
-        out = a.to_host(hist).reshape(K, days, _eng.COUNTER_WORDS)
+        c.day = start_day + days
+    out = hist.to_host()
     _t('history on the host')
     torch = getattr(a, 'torch', None)
     if torch is not None:

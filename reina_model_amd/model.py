@@ -22,6 +22,7 @@ from datetime import date, timedelta
 
 import numpy as np
 
+from . import dayrun as _dayrun
 from . import engine as _eng
 from .contacts import ContactMatrix, PLACES
 
@@ -410,13 +411,11 @@ class Context:
         self.transmission_log = _txl.TransmissionLog(self)
         return self.transmission_log
 
-    def _run_day_array(self, arr, n, history_ptr):
-        """engine.run_day_array, or the logged entry point when a log is attached"""
+    @property
+    def _sink(self):
+        """where this Context's days go (dayrun.py): the engine, or the device log when one is attached"""
         log = self.transmission_log
-        if log is None:
-            self.engine.run_day_array(arr, n, history_ptr)
-        else:
-            log.device.run_day_array(arr, n, history_ptr)
+        return self.engine if log is None else log.device
 
     def _set_initial_state(self, ipc):
         """Population.set_initial_state (main.pyx:1452-1516) on the engine; a sharded population
@@ -456,10 +455,15 @@ class Context:
     def _packed_tables(self):
         t = self.contact_matrix.tables
         nrc, count, thr, meta, ranges = pack_contact_tables(t, self.nr_ages)
+        return nrc, count, thr, meta, Context._mask_block(self), ranges
+
+    def _mask_block(self):
+        """the mask shares as an upload carries them; they take effect when tables are uploaded, so this is also what a
+        snapshot carries (`_uploaded_mask`).  (Called unbound on policy._MatrixHolder too.)"""
         mask = np.zeros((_eng.MAX_AGES, 8), dtype=np.float32)
         mask[:self.nr_ages, :6] = self.contact_matrix.mask_probabilities.astype(np.float32)
-        self._uploaded_mask = mask   # (mask shares take effect when tables are uploaded: what a snapshot carries)
-        return nrc, count, thr, meta, mask, ranges
+        self._uploaded_mask = mask
+        return mask
 
     def _upload_tables(self):
         self.engine.upload_contact_tables(*self._packed_tables())
@@ -700,77 +704,28 @@ class Context:
         if self.transmission_log is not None and not self.transmission_log.on_device:
             raise ValueError('run_plan: this Context keeps its log on the host (txlog.run_host_driven runs its days)')
         days = plan['days']
-        a = self.engine.alloc
         self._replayed = True
-        hist = self._history_buffer(days) if record_history else None
-        base = a.ptr(hist) if record_history else None
-        done = 0
-        for tables, arr, n in plan['segments']:
+        hist = _dayrun.History(days, record_history, ctx=self)
+
+        def upload(si, tables):
             if tables is not None:
                 self.engine.upload_contact_tables(*tables)
-            ptr = base + 4 * _eng.COUNTER_WORDS * done if record_history else None
-            self._run_day_array(arr, n, ptr)
-            done += n
+
+        _dayrun.replay_plan(plan, self._sink, hist, upload)
         self.mobility_history = plan['mobility_history']
         self.day = plan['start_day'] + days
-        if record_history:
-            return self._history_to_host(hist, days)
-        return None
-
-    def _history_buffer(self, days):
-        """`days` history rows (each written whole by its day's opening launch: no memset); they come back together with the
-        counters after the last day in one library call (engine.read_history)"""
-        return self.engine.alloc.empty(max(days, 1) * _eng.COUNTER_WORDS, np.int32)
-
-    def _history_to_host(self, hist, days):
-        out = self.engine.read_history(hist, days)
-        self._raise_on_problem(out[days])
-        return out[:days]
+        return hist.to_host()
 
     def _run_streamed(self, days, record_history):
         """run() for an unsharded population, or a sharded one whose engine queues the per-day
         all-reduce itself (reina_set_collective): day descriptors are built on the host and handed to
-        the library in growing chunks (1, 2, 4, ... 64 days), so the GPU works on the first days while the host is still
+        the library in growing chunks (dayrun.stream_days), so the GPU works on the first days while the host is still
         turning the intervention schedule into the later ones (table uploads are queued copies from
         pinned staging, they do not drain the stream either)."""
-        a = self.engine.alloc
-        single = self.n_shards == 1 and not self.always_collective
-        hist = None
-        if record_history:
-            hist = self._history_buffer(days) if single else a.zeros(days * _eng.COUNTER_WORDS, np.int32)
-        base = a.ptr(hist) if record_history else None
-        row = 4 * _eng.COUNTER_WORDS
-        self.mobility_history = []
-        pending, issued, chunk = [], 0, 1   # (1, 2, 4, ... 64 days per call: day 0 runs on the GPU while day 1 is being planned)
-
-        def flush():
-            nonlocal pending, issued, chunk
-            if pending:
-                arr = (_eng.Day * len(pending))(*pending)
-                self._run_day_array(arr, len(pending), base + row * issued if record_history else None)
-                issued += len(pending)
-                pending = []
-                chunk = min(chunk * 2, 64)
-
-        for _ in range(days):
-            self.mobility_history.append(float(self.contact_matrix.mobility_factor))
-            d, changed = self._build_day(None)
-            if changed:
-                flush()
-                self.engine.upload_contact_tables(*self._packed_tables())
-            pending.append(d)
-            self.day += 1
-            if len(pending) >= chunk:
-                flush()
-        flush()
-        if record_history:
-            if single:
-                out = self._history_to_host(hist, days)
-            else:   # sharded: rows are summed over the shards when exported
-                out = self._reduce_counter_rows(hist, days)
-                self._raise_on_problem(self._read_counters_global())
-            return out
-        return None
+        hist = _dayrun.History(days, record_history, ctx=self)
+        self.mobility_history = _dayrun.stream_days(self, days, self._sink, hist,
+                                                    lambda d, changed: self._upload_tables if changed else None)
+        return hist.to_host()
 
     def run(self, days, record_history=True):
         """Run `days` consecutive days with one library call per stretch of unchanged contact
@@ -790,23 +745,16 @@ class Context:
             return _txl.run_host_driven(self, days, record_history)
         if self._in_stream or (self.n_shards == 1 and not self.always_collective):
             return self._run_streamed(days, record_history)
-        a = self.engine.alloc
-        hist = a.zeros(days * _eng.COUNTER_WORDS, np.int32) if record_history else None
-        base = a.ptr(hist) if record_history else 0
+        hist = _dayrun.History(days, record_history, ctx=self)
         self.mobility_history = []
         for k in range(days):
-            ptr = base + 4 * _eng.COUNTER_WORDS * k if record_history else None
             self.mobility_history.append(float(self.contact_matrix.mobility_factor))
-            d, changed = self._build_day(ptr)
+            d, changed = self._build_day(hist.at(k))
             if changed:
                 self._upload_tables()
             self._step(d)
             self.day += 1
-        if record_history:
-            out = self._reduce_counter_rows(hist, days)
-            self._raise_on_problem(self._read_counters_global())
-            return out
-        return None
+        return hist.to_host()
 
     def synchronize(self):
         self._raise_on_problem(self._read_counters_global())

@@ -40,6 +40,7 @@ from datetime import date
 import numpy as np
 
 from . import engine as _eng
+from .dayrun import History, replay_plan, stream_days
 
 POLICY_VERSION = 1
 MAX_LEVELS = 8
@@ -245,11 +246,11 @@ def mobility_trace(first_value, segment_of_day, levels, factors):
     return out[:len(levels)]
 
 
-def _first_mobility(ctx, dated):
-    """what a policy run's first day reports: the value the Context's last policy run left if this run continues it, else the
-    dated one"""
+def _first_mobility(ctx, dated, day):
+    """what a policy run that begins on `day` reports on its first day: the value the Context's last policy run left if this
+    run continues it, else the dated one"""
     carried = getattr(ctx, '_policy_mobility', None)
-    return carried[1] if carried is not None and carried[0] == ctx.day else float(dated)
+    return carried[1] if carried is not None and carried[0] == day else float(dated)
 
 
 def _finish(ctx, first_value, levels, segment_of_day, factors, end_day):
@@ -265,9 +266,16 @@ def _finish(ctx, first_value, levels, segment_of_day, factors, end_day):
 
 def _note_dated_upload(ctx):
     """a day rebuilt the dated tables: their upload would carry the mask shares as they stand (Context._packed_tables)"""
-    mask = np.zeros((_eng.MAX_AGES, 8), dtype=np.float32)
-    mask[:ctx.nr_ages, :6] = ctx.contact_matrix.mask_probabilities.astype(np.float32)
-    ctx._uploaded_mask = mask
+    ctx._mask_block()
+
+
+def _end_device_run(ctx, trace, member, start_day, dated_first, segment_of_day, factors):
+    """The end of a device run for one Context: `trace` (DevicePolicy.read_trace, the run's wait) of `member` becomes its
+    policy_signal, policy_levels and mobility_history.  dated_first: the dated mobility factor before the first day."""
+    days = trace.shape[1]
+    first_value = _first_mobility(ctx, dated_first, start_day) if days else 0.0
+    ctx.policy_signal = trace[member, :, 1].copy()
+    _finish(ctx, first_value, trace[member, :, 0], segment_of_day, factors, start_day + days)
 
 
 def check_capable(ctx):
@@ -286,17 +294,14 @@ def run_host_driven(ctx, policy, days, record_history=True):
     state = getattr(ctx, '_policy_state', None)
     if state is None or state['policy'] is not policy:
         state = ctx._policy_state = policy.new_state(ctx.start_date)
-    a = ctx.engine.alloc
-    hist = ctx._history_buffer(days) if record_history else None
-    base = a.ptr(hist) if record_history else None
-    row = 4 * _eng.COUNTER_WORDS
+    hist = History(days, record_history, ctx=ctx)
     levels, seg_of_day, factors = [], [], []
     bank, in_force = None, None
-    first_value = _first_mobility(ctx, ctx.contact_matrix.mobility_factor)
+    first_value = _first_mobility(ctx, ctx.contact_matrix.mobility_factor, ctx.day)
     for k in range(days):
         counters = ctx.engine.read_counters()
         level = step_numpy(state, counters, ctx.day)
-        d, changed = ctx._build_day(base + row * k if record_history else None)
+        d, changed = ctx._build_day(hist.at(k))
         if changed:
             _note_dated_upload(ctx)
         if changed or bank is None:
@@ -311,10 +316,14 @@ def run_host_driven(ctx, policy, days, record_history=True):
         levels.append(level)
         seg_of_day.append(len(factors) - 1)
     _finish(ctx, first_value, levels, seg_of_day, factors, ctx.day)
-    if record_history:
-        return ctx._history_to_host(hist, days)
-    ctx.synchronize()
-    return None
+    return _history_or_wait(ctx, hist)
+
+
+def _history_or_wait(ctx, hist):
+    """a policy run ends with a wait either way: for its history, or (record_history=False) for the counters"""
+    if hist.buf is None:
+        ctx.synchronize()
+    return hist.to_host()
 
 
 # ------------------------------------------------------------------------------------------------ the device route
@@ -359,10 +368,7 @@ class DevicePolicy:
     def run_day_array(self, arr, n, history):
         """history: a device pointer (one engine) or one per member (a group), or None"""
         if self._grouped:
-            _eng.mark_stale(self.group.engines)
-            hp = None
-            if history is not None:
-                hp = (ctypes.c_void_p * self.members)(*[int(p) for p in history])
+            hp = _eng.member_pointers(self.group.engines, history)
             self.owner._check(self.f['group_policy_run_days'](self._h, arr, n, hp, self.alloc.stream()), 'group_policy_run_days')
         else:
             self.owner._check(self.f['policy_run_days'](self._h, arr, n, history, self.alloc.stream()), 'policy_run_days')
@@ -390,50 +396,28 @@ def _device_of(ctx):
 
 def run_device(ctx, days, record_history=True):
     """Context.run for a Context with a policy attached: day descriptors are built on the host and handed to the library in
-    growing chunks (1, 2, 4, ... 64 days, as Context._run_streamed does), k_policy ahead of every day, a bank of level tables
-    at every stretch of dated tables; one wait at the end, which brings the trace back with the history."""
+    growing chunks (dayrun.stream_days), k_policy ahead of every day, a bank of level tables at every stretch of dated tables
+    and on the run's first day; one wait at the end, which brings the trace back with the history."""
     check_capable(ctx)
     dev, policy = _device_of(ctx), ctx.policy
-    a = ctx.engine.alloc
-    hist = ctx._history_buffer(days) if record_history else None
-    base = a.ptr(hist) if record_history else None
-    row = 4 * _eng.COUNTER_WORDS
+    hist = History(days, record_history, ctx=ctx)
     start_day = ctx.day
-    first_value = _first_mobility(ctx, ctx.contact_matrix.mobility_factor)
     seg_of_day, factors = [], []
-    pending, issued, chunk = [], 0, 1
 
-    def flush():
-        nonlocal pending, issued, chunk
-        if pending:
-            arr = (_eng.Day * len(pending))(*pending)
-            dev.run_day_array(arr, len(pending), base + row * issued if record_history else None)
-            issued += len(pending)
-            pending = []
-            chunk = min(chunk * 2, 64)
-
-    for _ in range(days):
-        d, changed = ctx._build_day(None)
+    def on_day(d, changed):
+        upload = None
         if changed:
             _note_dated_upload(ctx)
         if changed or not factors:
-            flush()
             bank, f = build_bank(ctx, policy)
             factors.append(f)
-            dev.upload_bank(bank)
-        pending.append(d)
+            upload = lambda: dev.upload_bank(bank)
         seg_of_day.append(len(factors) - 1)
-        ctx.day += 1
-        if len(pending) >= chunk:
-            flush()
-    flush()
-    trace = dev.read_trace(start_day, days)
-    ctx.policy_signal = trace[0, :, 1].copy()
-    _finish(ctx, first_value, trace[0, :, 0], seg_of_day, factors, ctx.day)
-    if record_history:
-        return ctx._history_to_host(hist, days)
-    ctx.synchronize()
-    return None
+        return upload
+
+    dated = stream_days(ctx, days, dev, hist, on_day)
+    _end_device_run(ctx, dev.read_trace(start_day, days), 0, start_day, dated[0] if days else 0.0, seg_of_day, factors)
+    return _history_or_wait(ctx, hist)
 
 
 def run_plan_device(ctx, plan, record_history=True):
@@ -442,22 +426,10 @@ def run_plan_device(ctx, plan, record_history=True):
     if banks is None or plan.get('policy') is not ctx.policy:
         raise ValueError('run_plan: this Context carries a policy; the plan must be made with it (make_plan(days, policy=...))')
     dev = _device_of(ctx)
-    days = plan['days']
-    ctx.day = plan['start_day']
-    first_value = _first_mobility(ctx, plan['mobility_history'][0]) if days else 0.0
-    a = ctx.engine.alloc
-    hist = ctx._history_buffer(days) if record_history else None
-    base = a.ptr(hist) if record_history else None
-    done = 0
-    for (tables, arr, n), bank in zip(plan['segments'], banks):
-        dev.upload_bank(bank[0])
-        dev.run_day_array(arr, n, base + 4 * _eng.COUNTER_WORDS * done if record_history else None)
-        done += n
-    trace = dev.read_trace(plan['start_day'], days)
-    ctx.policy_signal = trace[0, :, 1].copy()
-    ctx.day = plan['start_day'] + days
-    _finish(ctx, first_value, trace[0, :, 0], plan_segments_of_days(plan), [b[1] for b in banks], ctx.day)
-    if record_history:
-        return ctx._history_to_host(hist, days)
-    ctx.synchronize()
-    return None
+    days, start_day = plan['days'], plan['start_day']
+    hist = History(days, record_history, ctx=ctx)
+    replay_plan(plan, dev, hist, lambda si, tables: dev.upload_bank(banks[si][0]))
+    ctx.day = start_day + days
+    _end_device_run(ctx, dev.read_trace(start_day, days), 0, start_day, plan['mobility_history'][0] if days else 0.0,
+                    plan_segments_of_days(plan), [b[1] for b in banks])
+    return _history_or_wait(ctx, hist)

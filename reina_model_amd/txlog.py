@@ -334,13 +334,11 @@ class DeviceLog:
 
     def run_day_array(self, arr, n, history):
         """Engine.run_day_array / EngineGroup.run_day_array with the record launch behind every day"""
-        self._touch()
         if self.group is None:
+            self._touch()
             self.engine._check(self.f['txlog_run_days'](self._h, arr, n, history, self.engine.alloc.stream()), 'txlog_run_days')
             return
-        hp = None
-        if history is not None:
-            hp = (ctypes.c_void_p * self.members)(*[int(p) for p in history])
+        hp = _eng.member_pointers(self.group.engines, history)
         self.engine._check(self.f['group_txlog_run_days'](self._h, arr, n, hp, self.engine.alloc.stream()), 'group_txlog_run_days')
 
     def words(self, member=0):

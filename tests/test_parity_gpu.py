@@ -1332,3 +1332,39 @@ def test_strict_iterate_raises_on_the_day_of_the_problem():
         lazy.iterate()
     with pytest.raises(SimulationFailed):
         lazy.generate_state()
+
+
+@pytest.mark.parametrize('attachment', ['plain', 'txlog', 'policy'])
+def test_every_route_of_the_day_runner_gives_the_same_days(attachment):
+    """70 days of the default scenario (chunks of 1 + 2 + 4 + 8 + 16 + 32 + 7 days, cut once more wherever the tables change)
+    by Context.run, by make_plan + run_plan, and as both members -- two Contexts of one seed -- of an engine group: identical
+    histories and identical final hot words, infector links, infection counts and onset durations, word for word; plain, with
+    a transmission log, and under a policy that never triggers."""
+    from policy_util import never_policy
+    from reina_model_amd import ensemble
+    v = copy.deepcopy(VARIABLE_DEFAULTS)
+    v.update(hospital_beds=12, icu_units=2)
+    ages, days, seed = datasets.scaled_population(20000), 70, 3
+    policy = never_policy() if attachment == 'policy' else None
+    log = attachment == 'txlog'
+    make = lambda **kw: simulation.make_context(v, age_counts=ages, seed=seed, **kw)
+    plan = make().make_plan(days, policy=policy)
+    runs = {}
+    ctx = make(policy=policy, txlog=log)
+    runs['run'] = (ctx, ctx.run(days))
+    ctx = make(policy=policy, txlog=log)
+    runs['run_plan'] = (ctx, ctx.run_plan(plan))
+    members = [make(), make()]
+    hist = ensemble.run_group_plan(members, plan, policy=policy, txlog=log)
+    runs['member 0'], runs['member 1'] = (members[0], hist[0]), (members[1], hist[1])
+    state = lambda c: [c.engine.alloc.to_host(c.engine.tensors[k]).view(np.uint32).copy()
+                       for k in ('hot', 'infector', 'n_infected', 'onset_days')]
+    want_hist, want_state = np.asarray(runs['run'][1]), state(runs['run'][0])
+    assert want_hist.shape == (days, eng.COUNTER_WORDS) and want_hist[-1, eng.C_NAMES.index('all_infected') * eng.MAX_AGES:][:eng.MAX_AGES].sum() > 0
+    for name, (c, h) in runs.items():
+        assert np.array_equal(np.asarray(h), want_hist), 'history of %s' % name
+        for k, a, b in zip(('hot', 'infector', 'n_infected', 'onset_days'), state(c), want_state):
+            assert np.array_equal(a, b), '%s of %s' % (k, name)
+        assert c.day == days and len(c.mobility_history) == days
+        if policy is not None:
+            assert not np.asarray(c.policy_levels).any()

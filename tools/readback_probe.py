@@ -1,13 +1,13 @@
 import copy, os, sys, time
 sys.path.insert(0, os.getcwd())
 import numpy as np, torch
-from reina_model_amd import datasets, simulation, engine as eng
+from reina_model_amd import datasets, dayrun, simulation, engine as eng
 from reina_model_amd.variables import VARIABLE_DEFAULTS
 ages = datasets.get_population_for_area()
 ctx = simulation.make_context(copy.deepcopy(VARIABLE_DEFAULTS), age_counts=ages, seed=1)
 ctx.run(25, record_history=True); torch.cuda.synchronize()
 e = ctx.engine; a = e.alloc
-hist = ctx._history_buffer(20)
+hist = dayrun.History(20, ctx=ctx).buf
 ctx.run(20, record_history=True); torch.cuda.synchronize()
 rows = 20; n = (rows + 1) * eng.COUNTER_WORDS
 acc = {}
