@@ -391,6 +391,9 @@ class Engine:
         # the dated transmission log (include/reina_txlog.h): likewise
         from .txlog import bind_txlog_abi
         self.txlog_f = bind_txlog_abi(lib, prefix)
+        # lineage reports of a log and its engine (include/reina_lineage.h): likewise
+        from .lineage import bind_lineage_abi
+        self.lineage_f = bind_lineage_abi(lib, prefix)
         self.config = config
         self._h = ctypes.c_void_p()
         self._check(self.f['create'](ctypes.byref(config), ctypes.byref(disease), ctypes.byref(self._h)), 'create')

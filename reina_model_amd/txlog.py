@@ -428,6 +428,14 @@ class TransmissionLog:
             w = report_numpy(_host_array(e.tensors['hot']), cold[:, 2], cold[:, 3], self.words(), ctx.age_start, table, n_days).words
         return LogReport(w, n_days, len(labels), labels, ctx.start_date)
 
+    def lineage_report(self, period=7, n_periods=None, age_groups=None):
+        """lineage.LineageReport between two days: who infects whom by period of `period` days, and the trees of the run by
+        the period they were seeded in.  n_periods: default the periods that hold the days run so far (at most 256:
+        ValueError beyond).  On the device when the library has the entry points and the log is there, lineage.report_numpy
+        on host copies otherwise.  Reads the engine's state and the log only."""
+        from . import lineage as _lin
+        return _lin.report_log(self, period, n_periods, age_groups)
+
     def line_list(self):
         """One row per infected agent (a pandas DataFrame, built on the host from the hot words, the cold records and the log):
         agent, age, infector (-1: an import or the initial condition), infector_age (-1 without one), infection_day and
