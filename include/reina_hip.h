@@ -262,8 +262,10 @@ typedef struct {
 /* Contact sampling tables for one rebuild (ContactMatrix.generate_contact_probabilities,
  * main.pyx:1184-1235), host arrays:
  *   nr_contacts_by_age[A]          float32(total contacts/day)
- *   count[A]                       entries per age (<= REINA_MAX_ENTRIES)
- *   threshold[A][REINA_MAX_ENTRIES] uint32 floor(cum_p * 2^32) (saturated), padded with 0xFFFFFFFF
+ *   count[A]                       entries per age (<= REINA_MAX_ENTRIES); 0 only for an age without contacts
+ *                                  (nr_contacts_by_age <= 0): anything else is refused with REINA_E_INVALID
+ *   threshold[A][REINA_MAX_ENTRIES] uint32 floor(cum_p * 2^32) (saturated), padded with 0xFFFFFFFF; non-decreasing
+ *                                  within an age (the caller's to keep: the searches rely on it), entries in any order
  *   meta[A][REINA_MAX_ENTRIES]      place | cmin << 8 | cmax << 16 | range_id << 24
  *   mask_p[A][8]                    float32 mask probability by (participant age, place)
  *   range_min/max[n_ranges]         the distinct contact age ranges, indexed by range_id */

@@ -206,9 +206,16 @@ int par_init_state(Par *e, int32_t beds, int32_t icu, void *stream) {
     return 0;
 }
 
+static char g_par_error[128];   /* text of the last refusal (par_last_error) */
 int par_upload_contact_tables(Par *e, const reina_contact_tables_t *t, void *stream) {
     (void)stream;
     uint32_t A = e->cfg.nr_ages;
+    for (uint32_t a = 0; a < A; a++)
+        if (t->count[a] == 0 && t->nr_contacts_by_age[a] > 0.0f) {   /* (run_contacts would index entry -1 of an empty row) */
+            snprintf(g_par_error, sizeof(g_par_error),
+                     "age %u has contacts (nr_contacts_by_age > 0) but no contact entries (count == 0)", a);
+            return REINA_E_INVALID;
+        }
     memcpy(e->nrc, t->nr_contacts_by_age, sizeof(float) * A);
     memcpy(e->tcount, t->count, sizeof(int32_t) * A);
     memcpy(e->thr, t->threshold, sizeof(uint32_t) * A * REINA_MAX_ENTRIES);
@@ -1415,7 +1422,7 @@ int par_profile_read_kernels(Par *e, double *ms, uint64_t *n) {
     for (int k = 0; k < REINA_PK_NR; k++) { ms[k] = 0; n[k] = 0; }
     return 0;
 }
-const char *par_last_error(void) { return ""; }
+const char *par_last_error(void) { return g_par_error; }
 
 /* the ABI's test hook on the host build of the primitives (include/reina_hip.h: reina_test_prims) */
 int par_test_prims(int what, const uint32_t *in, uint32_t n, uint32_t *out) {

@@ -551,6 +551,11 @@ static int derive_contact_tables(const reina_engine_t *e, const reina_contact_ta
             g_last_error = "contact entries per age must be in [0, REINA_MAX_ENTRIES]";
             return REINA_E_INVALID;
         }
+    for (uint32_t a = 0; a < A; a++)
+        if (t->count[a] == 0 && t->nr_contacts_by_age[a] > 0.0f) {   // (k_day would read entry 0 of an empty row)
+            g_last_error = "age " + std::to_string(a) + " has contacts (nr_contacts_by_age > 0) but no contact entries (count == 0)";
+            return REINA_E_INVALID;
+        }
     if (e->cfg.n_shards > 1 && t->n_ranges >= REINA_MAX_RANGES) {
         g_last_error = "a sharded engine takes at most REINA_MAX_RANGES - 1 contact ranges (the last range's pressure words carry free capacity)";
         return REINA_E_INVALID;
