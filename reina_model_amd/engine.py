@@ -376,24 +376,13 @@ class Engine:
     def __init__(self, lib, prefix, allocator, config, disease):
         self.f = bind_abi(lib, prefix)
         self.alloc = allocator
-        # snapshots (include/reina_snapshot.h): bound when the library has them, None otherwise
-        from .snapshot import bind_snapshot_abi
-        self.snap_f = bind_snapshot_abi(lib, prefix)
-        # transmission-tree reports (include/reina_transmission.h): likewise
-        from .transmission import bind_tx_abi
-        self.tx_f = bind_tx_abi(lib, prefix)
-        # the particle filter's in-group clone (include/reina_filter.h): likewise
-        from .filtering import bind_filter_abi
-        self.filter_f = bind_filter_abi(lib, prefix)
-        # triggered interventions (include/reina_policy.h): likewise
-        from .policy import bind_policy_abi
-        self.policy_f = bind_policy_abi(lib, prefix)
-        # the dated transmission log (include/reina_txlog.h): likewise
-        from .txlog import bind_txlog_abi
-        self.txlog_f = bind_txlog_abi(lib, prefix)
-        # lineage reports of a log and its engine (include/reina_lineage.h): likewise
-        from .lineage import bind_lineage_abi
-        self.lineage_f = bind_lineage_abi(lib, prefix)
+        # the headers beside reina_hip.h (snapshots, transmission-tree reports, the particle filter's in-group clone, triggered
+        # interventions, the dated transmission log, lineage reports): each bound when the library has it, None otherwise
+        from . import filtering, lineage, policy, snapshot, transmission, txlog
+        for attr, bind in (('snap_f', snapshot.bind_snapshot_abi), ('tx_f', transmission.bind_tx_abi),
+                           ('filter_f', filtering.bind_filter_abi), ('policy_f', policy.bind_policy_abi),
+                           ('txlog_f', txlog.bind_txlog_abi), ('lineage_f', lineage.bind_lineage_abi)):
+            setattr(self, attr, bind(lib, prefix))
         self.config = config
         self._h = ctypes.c_void_p()
         self._check(self.f['create'](ctypes.byref(config), ctypes.byref(disease), ctypes.byref(self._h)), 'create')

@@ -338,6 +338,15 @@ def transmission_reports(contexts, age_groups=None, group=None):
     return reps
 
 
+def _logged_group(contexts):
+    """the txlog.DeviceLog these contexts share when they are the whole logged group, in member order; None otherwise"""
+    glog = contexts[0].transmission_log.device
+    if glog is not None and glog.group is not None and all(c.transmission_log.device is glog for c in contexts) \
+            and [c.transmission_log.member for c in contexts] == list(range(glog.members)):
+        return glog
+    return None
+
+
 def log_reports(contexts, age_groups=None, n_days=None):
     """txlog.LogReport of every context, between the same two days.  The members of a logged group (run_group_plan(...,
     txlog=True)) are reported by ONE launch (reina_group_txlog_report); contexts that keep logs of their own one by one."""
@@ -345,9 +354,8 @@ def log_reports(contexts, age_groups=None, n_days=None):
     contexts = list(contexts)
     if any(c.transmission_log is None for c in contexts):
         raise ValueError('log_reports: a context keeps no transmission log')
-    glog = contexts[0].transmission_log.device
-    if glog is not None and glog.group is not None and all(c.transmission_log.device is glog for c in contexts) \
-            and [c.transmission_log.member for c in contexts] == list(range(glog.members)):
+    glog = _logged_group(contexts)
+    if glog is not None:
         return _txl.report_group(glog, contexts, age_groups, n_days)
     return [c.transmission_log.report(age_groups, n_days) for c in contexts]
 
@@ -360,9 +368,7 @@ def lineage_reports(contexts, period=7, n_periods=None, age_groups=None):
     contexts = list(contexts)
     if any(c.transmission_log is None for c in contexts):
         raise ValueError('lineage_reports: a context keeps no transmission log')
-    glog = contexts[0].transmission_log.device
-    if glog is not None and glog.group is not None and all(c.transmission_log.device is glog for c in contexts) \
-            and [c.transmission_log.member for c in contexts] == list(range(glog.members)) \
-            and getattr(glog.engine, 'lineage_f', None) is not None:
+    glog = _logged_group(contexts)
+    if glog is not None and getattr(glog.engine, 'lineage_f', None) is not None:
         return _lin.report_group(glog, contexts, period, n_periods, age_groups)
     return [c.transmission_log.lineage_report(period, n_periods, age_groups) for c in contexts]

@@ -33,7 +33,8 @@ import ctypes
 import numpy as np
 
 from . import engine as _eng
-from . import transmission as _tx
+from . import reports as _rep
+from . import transmission as _tx  # noqa: F401  (rounds_for is read as lineage._tx.rounds_for)
 from . import txlog as _txl
 
 LINEAGE_VERSION = 1            # include/reina_lineage.h: REINA_LINEAGE_VERSION
@@ -89,12 +90,20 @@ def bind_lineage_abi(lib, prefix):
                                   'lineage_version', LINEAGE_VERSION)
 
 
-def check_periods(period_days, n_periods):
-    period_days, n_periods = int(period_days), int(n_periods)
+def default_periods(day, period_days):
+    """ceil(max(day, 1) / period_days): the periods that hold every day run so far"""
+    return -(-max(int(day), 1) // int(period_days))
+
+
+def check_periods(period_days, n_periods, day=None):
+    """(period_days, n_periods) as integers in their ranges: the one statement of them, which every route takes before it
+    builds or launches anything.  n_periods None: default_periods(day, period_days)"""
+    period_days = int(period_days)
     if not 1 <= period_days <= _eng.MAX_DAYS:
-        raise ValueError('period_days must be in [1, %d]' % _eng.MAX_DAYS)
+        raise ValueError('period must be in [1, %d] days' % _eng.MAX_DAYS)
+    n_periods = default_periods(day, period_days) if n_periods is None else int(n_periods)
     if not 1 <= n_periods <= MAX_PERIODS:
-        raise ValueError('n_periods must be in [1, %d]' % MAX_PERIODS)
+        raise ValueError('n_periods = %d: a lineage report holds 1 .. %d periods (take a longer period)' % (n_periods, MAX_PERIODS))
     return period_days, n_periods
 
 
@@ -116,28 +125,15 @@ def report_numpy(hot, infector, n_infected, log, age_start, age_group, period_da
     n = len(hot)
     period_days, P = check_periods(period_days, n_periods)
     Q = P + 1
-    src = np.asarray(infector).view(np.int32).ravel().astype(np.int64)
     log = np.asarray(log, dtype=np.uint32).ravel()
-    age_start = np.asarray(age_start, dtype=np.int64).ravel()
-    nr_ages = min(len(np.asarray(age_group).ravel()), _eng.MAX_AGES, len(age_start) - 1)
-    table, n_groups = _tx._group_table(age_group, nr_ages)
-    max_depth = n if max_depth is None else int(max_depth)
-    rounds = _tx.rounds_for(max_depth)
+    table, n_groups, _, ages = _rep.age_lookup(age_start, age_group)
+    rounds = _rep.rounds_for(n if max_depth is None else max_depth)
     words = np.zeros(report_words(P), dtype=np.uint64)
 
-    # the links, as transmission.report_numpy and txlog.report_numpy classify them
-    state = hot & 7
-    idx = np.flatnonzero(state != 0)
+    state, idx, s, root, linked, bad = _rep.links(hot, infector)
     st = state[idx].astype(np.int64)
-    s = src[idx]
-    root = s == -1
-    in_range = (s >= 0) & (s < n) & (s != idx)
-    linked = np.zeros(len(idx), dtype=bool)
-    linked[in_range] = state[s[in_range]] != 0
-    bad = ~root & ~linked
     pc = period_class(log & 0xFFFF, period_days, P)      # of every agent
     ci = pc[idx]
-    ages = lambda i: np.clip(np.searchsorted(age_start[:nr_ages + 1], i, side='right') - 1, 0, nr_ages - 1)
     g = table[ages(idx)].astype(np.int64)
 
     a, b = cohort_offset(P), lineage_offset(P)
@@ -152,13 +148,8 @@ def report_numpy(hot, infector, n_infected, log, age_start, age_group, period_da
     words[b:c] = np.bincount(pc[sl] * MAX_GROUPS * MAX_GROUPS + cell, minlength=c - b).astype(np.uint64)
 
     # the trees: pointer jumping as k_tx_jump runs it
-    parent = np.full(n, _tx._MARK, dtype=np.uint32)
-    dist = np.zeros(n, dtype=np.uint32)
-    parent[idx] = np.where(linked, s, idx).astype(np.uint32)
-    dist[idx] = np.where(linked, 1, _tx._ROOTED).astype(np.uint32)
-    parent, dist = _tx._jump(parent, dist, rounds)
-    conv = (dist[idx] & _tx._ROOTED) != 0
-    r = parent[idx][conv].astype(np.int64)               # the root of every converged agent
+    r, _, conv = _rep.forest(n, idx, s, linked, rounds)
+    r = r[conv]                                          # the root of every converged agent
     alive = ((st >= S_INCUBATION) & (st <= S_IN_ICU))[conv]
     sc = pc[r]
     a, b = lineage_offset(P), mixing_t_offset(P)
@@ -179,12 +170,7 @@ def report_numpy(hot, infector, n_infected, log, age_start, age_group, period_da
     val = dict(infected=len(idx), links=int(linked.sum()), bad_links=int(bad.sum()), roots=int(root.sum()), trees=len(heads),
                unconverged=int((~conv).sum()), rounds=rounds, alive_agents=int(alive.sum()),
                alive_trees=int((size_alive[heads] > 0).sum()), undated=int((ci == P).sum()))
-    if len(heads):
-        big = int(hs.max())
-        r0 = int(heads[hs == big][0])
-        val.update(largest_tree=big, largest_root=r0, largest_key=big << 32 | (~r0 & 0xFFFFFFFF))
-    else:
-        val.update(largest_tree=0, largest_root=(1 << 64) - 1, largest_key=0)
+    val['largest_tree'], val['largest_root'], val['largest_key'] = _rep.largest(heads, hs)
     for k, name in enumerate(SCALAR_NAMES):
         words[SCALARS + k] = val[name]
     return LineageReport(words, period_days, P, n_groups)
@@ -192,17 +178,16 @@ def report_numpy(hot, infector, n_infected, log, age_start, age_group, period_da
 
 # ------------------------------------------------------------------------------------------------ reports
 
-class LineageReport:
+class LineageReport(_rep.Report):
     """One report: the words of include/reina_lineage.h as named arrays, plus what is derived from them on the host."""
+    SCALARS, SCALAR_NAMES, IDENTITY = SCALARS, SCALAR_NAMES, ('period_days', 'n_periods')
 
     def __init__(self, words, period_days, n_periods, n_groups=MAX_GROUPS, group_labels=None, start_date=None):
-        w = np.asarray(words, dtype=np.uint64).ravel()
-        self.period_days, P = check_periods(period_days, n_periods)
-        if len(w) != report_words(P):
-            raise ValueError('a lineage report of %d periods has %d words' % (P, report_words(P)))
+        self.period_days, self.n_periods = check_periods(period_days, n_periods)
+        P = self.n_periods
+        w = self._take(words, report_words(P), 'a lineage report of %d periods has %d words' % (P, report_words(P)), n_groups,
+                       group_labels)
         Q = P + 1
-        self.words, self.n_periods, self.n_groups = w, P, int(n_groups)
-        self.group_labels = list(group_labels) if group_labels is not None else None
         self.start_date = start_date
         o = [seed_offset(P), tree_sizes_offset(P), cohort_offset(P), lineage_offset(P), mixing_t_offset(P), mixing_c_offset(P),
              report_words(P)]
@@ -212,21 +197,10 @@ class LineageReport:
         self.lineage = w[o[3]:o[4]].reshape(Q, Q)
         self.mixing_t = w[o[4]:o[5]].reshape(Q, MAX_GROUPS, MAX_GROUPS)
         self.mixing_c = w[o[5]:o[6]].reshape(Q, MAX_GROUPS, MAX_GROUPS)
-        for k, name in enumerate(SCALAR_NAMES):
-            setattr(self, name, int(w[SCALARS + k]))
-        if self.largest_root == (1 << 64) - 1:
-            self.largest_root = -1
-
-    def __eq__(self, other):
-        return isinstance(other, LineageReport) and (self.period_days, self.n_periods) == (other.period_days, other.n_periods) \
-            and np.array_equal(self.words, other.words)
 
     def __repr__(self):
         return 'LineageReport(periods=%d x %d d, infected=%d, trees=%d, alive_trees=%d, largest_tree=%d)' % (
             self.n_periods, self.period_days, self.infected, self.trees, self.alive_trees, self.largest_tree)
-
-    def _groups(self):
-        return self.group_labels or [str(k) for k in range(self.n_groups)]
 
     def _periods(self, name, before=True):
         """the index of the P periods (their first day, or its date), with 'before' for class P"""
@@ -305,88 +279,49 @@ class LineageReport:
 
 # ------------------------------------------------------------------------------------------------ taking a report
 
-def _lineage_f(engine):
-    f = getattr(engine, 'lineage_f', None)
-    if f is None:
-        raise _eng.EngineError('the engine library has no lineage-report entry points (include/reina_lineage.h)')
-    return f
+_UNCONVERGED = SCALARS + SCALAR_NAMES.index('unconverged')
 
 
-def default_periods(day, period_days):
-    """ceil(max(day, 1) / period_days): the periods that hold every day run so far"""
-    return -(-max(int(day), 1) // int(period_days))
-
-
-def device_words(device_log, table, n_groups, period_days, n_periods, max_depth):
-    """[members, report_words(n_periods)] uint64 of a txlog.DeviceLog: one launch per pass for all members"""
+def _device_words(device_log, table, n_groups, period_days, n_periods):
+    """take(max_depth) of a txlog.DeviceLog for reports.with_deep_pass: one launch per pass for all members"""
     e = device_log.engine
-    f = _lineage_f(e)
-    torch, dev = e.alloc.torch, e.alloc.device
-    K, n = device_log.members, e.config.n_agents
-    scratch = [torch.empty(scratch_bytes(n), dtype=torch.uint8, device=dev) for _ in range(K)]
-    rep = torch.empty(K * report_words(n_periods), dtype=torch.int64, device=dev)
-    if device_log.group is None:
-        e._check(f['lineage_report'](device_log._h, table.ctypes.data, int(n_groups), int(period_days), int(n_periods), int(max_depth),
-                                     scratch[0].data_ptr(), rep.data_ptr(), e.alloc.stream()), 'lineage_report')
-    else:
-        ptrs = (ctypes.c_void_p * K)(*[s.data_ptr() for s in scratch])
-        e._check(f['group_lineage_report'](device_log._h, table.ctypes.data, int(n_groups), int(period_days), int(n_periods),
-                                           int(max_depth), ptrs, rep.data_ptr(), e.alloc.stream()), 'group_lineage_report')
-    device_log._touch()
-    words = rep.cpu().numpy().view(np.uint64).reshape(K, report_words(n_periods))
-    del scratch
-    return words
+    f = _rep.entry_points(e, 'lineage_f', 'lineage-report', 'reina_lineage.h')
+    group = device_log.group is not None
+    name = 'group_lineage_report' if group else 'lineage_report'
+    return lambda depth: _rep.device_words(
+        e, f, name, (device_log._h, table.ctypes.data, int(n_groups), int(period_days), int(n_periods), int(depth or 0)),
+        device_log.members, report_words(n_periods), scratch_bytes(e.config.n_agents), device_log.engines, group)
 
 
 def _arguments(ctx, period, n_periods, age_groups):
+    """(table, labels, period_days, n_periods) of a Context's route: its report groups, the periods checked (check_periods)"""
     table, labels = ctx._tx_groups(age_groups)
-    period = int(period)
-    if not 1 <= period <= _eng.MAX_DAYS:
-        raise ValueError('period must be in [1, %d] days' % _eng.MAX_DAYS)
-    n_periods = default_periods(ctx.day, period) if n_periods is None else int(n_periods)
-    if not 1 <= n_periods <= MAX_PERIODS:
-        raise ValueError('n_periods = %d: a lineage report holds 1 .. %d periods (take a longer period)' % (n_periods, MAX_PERIODS))
-    return table, labels, period, n_periods
-
-
-_UNCONVERGED = SCALARS + SCALAR_NAMES.index('unconverged')
+    return (table, labels) + check_periods(period, n_periods, ctx.day)
 
 
 def report_log(tlog, period=7, n_periods=None, age_groups=None):
     """TransmissionLog.lineage_report: the library's kernels when it has the entry points and the log is a single engine's on
     the device, report_numpy on host copies otherwise.  Generations are resolved to the engine's day + 1 first; a state deeper
-    than that (only a synthetic one can be) is reported again with every chain resolved."""
+    than that (only a synthetic one can be) is reported again with every chain resolved (reports.with_deep_pass)."""
     ctx = tlog.ctx
-    table, labels, period, P = _arguments(ctx, period, n_periods, age_groups)
-    e = ctx.engine
-    n = e.config.n_agents
     dlog = tlog.device
-    if dlog is not None and dlog.group is None and getattr(e, 'lineage_f', None) is not None:
-        t8, ng = _tx._group_table(table, ctx.nr_ages)
-        ng = max(ng, len(labels))
-        w = device_words(dlog, t8, ng, period, P, 0)[0]
-        if w[_UNCONVERGED]:
-            w = device_words(dlog, t8, ng, period, P, n)[0]
-    else:
-        host = _txl._host_array
-        hot = host(e.tensors['hot'])
-        cold = host(e.tensors['cold']).view(np.uint32).reshape(n, _eng.COLD_WORDS)
-        args = (hot, cold[:, 2], cold[:, 3], tlog.words(), ctx.age_start, table, period, P)
-        w = report_numpy(*args, _tx._day_depth(host(e.tensors['counters']))).words
-        if w[_UNCONVERGED]:
-            w = report_numpy(*args, n).words
+    if dlog is not None and dlog.group is None and getattr(ctx.engine, 'lineage_f', None) is not None:
+        return report_group(dlog, [ctx], period, n_periods, age_groups)[0]
+    table, labels, period, P = _arguments(ctx, period, n_periods, age_groups)
+    hot, inf, cnt, counters = _rep.host_state(ctx.engine)
+    log = tlog.words()
+    take = lambda depth: report_numpy(hot, inf, cnt, log, ctx.age_start, table, period, P,
+                                      depth or _rep.day_depth(counters)).words[None]
+    w = _rep.with_deep_pass(take, _UNCONVERGED, len(hot))[0]
     return LineageReport(w, period, P, len(labels), labels, ctx.start_date)
 
 
 def report_group(device_log, contexts, period=7, n_periods=None, age_groups=None):
-    """The reports of every member of a logged group: one launch per pass for all members (and once more, with every chain
-    resolved, when a member's first pass leaves agents unconverged)."""
+    """The reports of every member of a logged group (or of the one engine of a device log): one launch per pass for all
+    members (and once more, with every chain resolved, when a member's first pass leaves agents unconverged)."""
     c0 = contexts[0]
     table, labels, period, P = _arguments(c0, period, n_periods, age_groups)
-    t8, ng = _tx._group_table(table, c0.nr_ages)
-    ng = max(ng, len(labels))
-    w = device_words(device_log, t8, ng, period, P, 0)
-    deep = np.flatnonzero(w[:, _UNCONVERGED])
-    if len(deep):
-        w[deep] = device_words(device_log, t8, ng, period, P, c0.engine.config.n_agents)[deep]
-    return [LineageReport(w[m].copy(), period, P, len(labels), labels, c.start_date) for m, c in enumerate(contexts)]
+    t8, ng = _rep._group_table(table, c0.nr_ages)
+    take = _device_words(device_log, t8, max(ng, len(labels)), period, P)
+    w = _rep.with_deep_pass(take, _UNCONVERGED, c0.engine.config.n_agents)
+    return [LineageReport(r, period, P, len(labels), labels, c.start_date) for r, c in zip(_rep.member_rows(w), contexts)]

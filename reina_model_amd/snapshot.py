@@ -19,6 +19,7 @@ import struct
 import numpy as np
 
 from . import engine as _eng
+from . import reports as _rep
 
 SNAPSHOT_VERSION = 2           # include/reina_snapshot.h: REINA_SNAPSHOT_VERSION
 MAGIC = 0x504E5352             # "RSNP"
@@ -189,10 +190,7 @@ def unpack_numpy(engine, disease, image):
 
 
 def _snap_f(engine):
-    f = getattr(engine, 'snap_f', None)
-    if f is None:
-        raise _eng.EngineError('the engine library has no snapshot entry points (include/reina_snapshot.h)')
-    return f
+    return _rep.entry_points(engine, 'snap_f', 'snapshot', 'reina_snapshot.h')
 
 
 def pack_engine(engine, disease, testing_ever):

@@ -14,6 +14,8 @@ import ctypes
 import numpy as np
 
 from . import engine as _eng
+from . import reports as _rep
+from .reports import _group_table, default_age_groups, rounds_for  # noqa: F401  (theirs since reports.py; used from here)
 
 TX_VERSION = 1                 # include/reina_transmission.h: REINA_TX_VERSION
 VARIANTS, SEVERITIES, OUTCOMES, BINS = 4, 5, 3, 64
@@ -37,22 +39,10 @@ SEVERITY_NAMES = ('asymptomatic', 'mild', 'severe', 'critical', 'fatal')
 
 TX_FUNCTIONS = ('tx_version', 'tx_report', 'group_tx_report')
 
-_ROOTED = 1 << 31
-_DIST_MAX = (1 << 31) - 1
-_MARK = 0xFFFFFFFF
-
 
 def scratch_bytes(n_agents):
     """include/reina_transmission.h: REINA_TX_SCRATCH_BYTES"""
     return (int(n_agents) * 20 + 255) & ~255
-
-
-def rounds_for(max_depth):
-    """pointer-jumping rounds that resolve every generation up to max_depth: ceil(log2(max_depth + 1))"""
-    r = 0
-    while (1 << r) < int(max_depth) + 1:
-        r += 1
-    return r
 
 
 def bind_tx_abi(lib, prefix):
@@ -62,56 +52,18 @@ def bind_tx_abi(lib, prefix):
     return _eng.bind_optional_abi(lib, prefix, TX_FUNCTIONS, argtypes, 'tx_version', TX_VERSION)
 
 
-def default_age_groups(nr_ages):
-    """10-year bins, 80+ (what the default population's report groups are)"""
-    g = np.minimum(np.arange(_eng.MAX_AGES) // 10, 8)
-    return g.astype(np.uint8), ['%d-%d' % (10 * k, 10 * k + 9) for k in range(8)] + ['80+']
-
-
-def _group_table(age_group, nr_ages):
-    """(uint8[MAX_AGES] table, n_groups) from a per-age sequence (ages beyond it: group 0)"""
-    g = np.asarray(age_group, dtype=np.int64).ravel()
-    if len(g) < nr_ages:
-        raise ValueError('age_group: %d ages given, the population has %d' % (len(g), nr_ages))
-    g = g[:nr_ages]
-    if len(g) and (g.min() < 0 or g.max() >= MAX_GROUPS):
-        raise ValueError('age groups are 0 .. %d' % (MAX_GROUPS - 1))
-    table = np.zeros(_eng.MAX_AGES, dtype=np.uint8)
-    table[:nr_ages] = g
-    return table, int(g.max()) + 1 if len(g) else 1
-
-
-def _jump(parent, dist, rounds):
-    """rounds of double-buffered pointer jumping, as k_tx_jump runs them"""
-    n = len(parent)
-    for _ in range(rounds):
-        go = (parent < n) & ((dist & _ROOTED) == 0)
-        p = np.where(go, parent, 0).astype(np.int64)
-        qp, qd = parent[p], dist[p]
-        s = np.minimum((dist & _DIST_MAX).astype(np.int64) + (qd & _DIST_MAX).astype(np.int64), _DIST_MAX).astype(np.uint32)
-        parent = np.where(go, qp, parent)
-        dist = np.where(go, s | (qd & _ROOTED), dist)
-    return parent, dist
-
-
 def report_numpy(hot, infector, n_infected, age_start, age_group, max_depth=None):
     """The report of one state (the specification of reina_tx_report).  hot: uint32[N]; infector, n_infected: int32[N] (the
     cold record's fields); age_start: first agent of each age ([A] = N, padded with N); age_group: group of each age
     (< MAX_GROUPS); max_depth: the deepest generation resolved (None: N, which every chain without a cycle fits)."""
     hot = np.asarray(hot).view(np.uint32).ravel()
     n = len(hot)
-    src = np.asarray(infector).view(np.int32).ravel().astype(np.int64)
     cnt = np.asarray(n_infected).view(np.uint32).ravel().astype(np.uint64)
-    age_start = np.asarray(age_start, dtype=np.int64).ravel()
-    nr_ages = min(len(np.asarray(age_group).ravel()), _eng.MAX_AGES, len(age_start) - 1)
-    table, n_groups = _group_table(age_group, nr_ages)
-    max_depth = n if max_depth is None else int(max_depth)
-    rounds = rounds_for(max_depth)
+    table, n_groups, _, ages = _rep.age_lookup(age_start, age_group)
+    rounds = rounds_for(n if max_depth is None else max_depth)
 
     words = np.zeros(REPORT_WORDS, dtype=np.uint64)
-    state = hot & 7
-    inf = state != 0
-    idx = np.flatnonzero(inf)
+    _, idx, s, root, linked, bad = _rep.links(hot, infector)
     w = hot[idx]
     v = ((w >> 8) & 3).astype(np.int64)
     sev = np.minimum((w >> 3) & 7, 4).astype(np.int64)
@@ -126,29 +78,15 @@ def report_numpy(hot, infector, n_infected, age_start, age_group, max_depth=None
         words[OFFSPRING_SUM + k] = int(sel.sum(dtype=np.uint64))
         words[OFFSPRING_SUMSQ + k] = int((sel * sel).sum(dtype=np.uint64))
 
-    s = src[idx]
-    root = s == -1
-    in_range = (s >= 0) & (s < n) & (s != idx)
-    linked = np.zeros(len(idx), dtype=bool)
-    linked[in_range] = state[s[in_range]] != 0
-    bad = ~root & ~linked
-    ages = lambda i: np.clip(np.searchsorted(age_start[:nr_ages + 1], i, side='right') - 1, 0, nr_ages - 1)
     li = idx[linked]
     gs, gi = table[ages(li)].astype(np.int64), table[ages(s[linked])].astype(np.int64)
     words[MATRIX:GENERATION] = np.bincount((v[linked] * MAX_GROUPS + gi) * MAX_GROUPS + gs,
                                            minlength=GENERATION - MATRIX).astype(np.uint64)
 
-    parent = np.full(n, _MARK, dtype=np.uint32)
-    dist = np.zeros(n, dtype=np.uint32)
-    parent[idx] = np.where(linked, s, idx).astype(np.uint32)
-    dist[idx] = np.where(linked, 1, _ROOTED).astype(np.uint32)
-    parent, dist = _jump(parent, dist, rounds)
-    p, d = parent[idx], dist[idx]
-    conv = (d & _ROOTED) != 0
-    gen = (d & _DIST_MAX).astype(np.int64)
+    p, gen, conv = _rep.forest(n, idx, s, linked, rounds)
     words[GENERATION:CLUSTERS] = np.bincount(v[conv] * GENERATIONS + np.minimum(gen[conv], GENERATIONS - 1),
                                              minlength=CLUSTERS - GENERATION).astype(np.uint64)
-    size = np.bincount(p[conv].astype(np.int64), minlength=n)
+    size = np.bincount(p[conv], minlength=n)
     roots = np.flatnonzero(size)
     rs = size[roots].astype(np.int64)
     b = np.floor(np.log2(np.maximum(rs, 1))).astype(np.int64)
@@ -158,34 +96,10 @@ def report_numpy(hot, infector, n_infected, age_start, age_group, max_depth=None
               sum_n_infected=int(words[OFFSPRING_SUM:OFFSPRING_SUMSQ].sum(dtype=np.uint64)),
               max_generation=int(gen[conv].max()) if conv.any() else 0, bad_links=int(bad.sum()),
               unconverged=int((~conv).sum()), rounds=rounds)
-    if len(roots):
-        big = int(rs.max())
-        r0 = int(roots[rs == big][0])
-        sc.update(largest_cluster=big, largest_root=r0, largest_key=big << 32 | (~r0 & 0xFFFFFFFF))
-    else:
-        sc.update(largest_cluster=0, largest_root=(1 << 64) - 1, largest_key=0)
+    sc['largest_cluster'], sc['largest_root'], sc['largest_key'] = _rep.largest(roots, rs)
     for k, name in enumerate(SCALAR_NAMES):
         words[SCALARS + k] = sc[name]
     return TransmissionReport(words, n_groups)
-
-
-def _host_fields(engine):
-    t = engine.tensors
-    n = engine.config.n_agents
-    cold = np.asarray(t['cold']).view(np.uint32).reshape(n, _eng.COLD_WORDS)
-    return np.asarray(t['hot']).view(np.uint32), cold[:, 2], cold[:, 3], np.asarray(t['counters'])
-
-
-def _day_depth(counters):
-    day = int(np.asarray(counters).view(np.int32)[_eng.C_NR * _eng.MAX_AGES + _eng.S_DAY])
-    return min(max(day, 0), _eng.MAX_DAYS) + 1
-
-
-def _tx_f(engine):
-    f = getattr(engine, 'tx_f', None)
-    if f is None:
-        raise _eng.EngineError('the engine library has no transmission-report entry points (include/reina_transmission.h)')
-    return f
 
 
 def _check_unsharded(config):
@@ -193,67 +107,45 @@ def _check_unsharded(config):
         raise ValueError('transmission reports are taken of unsharded engines only')
 
 
-def _device_report(engine, table, n_groups, max_depth):
-    f = _tx_f(engine)
-    torch = engine.alloc.torch
-    dev = engine.alloc.device
-    scratch = torch.empty(scratch_bytes(engine.config.n_agents), dtype=torch.uint8, device=dev)
-    rep = torch.empty(REPORT_WORDS, dtype=torch.int64, device=dev)
-    engine._check(f['tx_report'](engine._h, table.ctypes.data, n_groups, int(max_depth), scratch.data_ptr(), rep.data_ptr(),
-                                 engine.alloc.stream()), 'tx_report')
-    return rep.cpu().numpy().view(np.uint64)
+_UNCONVERGED = SCALARS + SCALAR_NAMES.index('unconverged')
+
+
+def _device_reports(engines, group, age_group, n_groups):
+    """the reports of `engines` by the library's kernels, one launch per pass: the members of `group`, or one engine (None)"""
+    e0 = engines[0]
+    for e in engines:
+        _check_unsharded(e.config)
+    table, ng = _group_table(age_group, e0.config.nr_ages)
+    ng = max(ng, int(n_groups or 0))
+    f = _rep.entry_points(e0, 'tx_f', 'transmission-report', 'reina_transmission.h')
+    name, handle = ('tx_report', e0._h) if group is None else ('group_tx_report', group._h)
+    n = e0.config.n_agents            # (of every member: an engine group is made of engines of one population)
+    take = lambda depth: _rep.device_words(e0, f, name, (handle, table.ctypes.data, ng, int(depth or 0)), len(engines), REPORT_WORDS,
+                                           scratch_bytes(n), engines, group is not None)
+    return [TransmissionReport(w, ng) for w in _rep.member_rows(_rep.with_deep_pass(take, _UNCONVERGED, n))]
 
 
 def report_engine(engine, age_group, n_groups=None):
     """The report of one engine: the library's kernels on a HIP engine, report_numpy on host views otherwise.  Generations
     are resolved to the engine's day + 1 first; a state deeper than that (only a synthetic one can be) is reported again with
-    every chain resolved."""
+    every chain resolved (reports.with_deep_pass)."""
     _check_unsharded(engine.config)
+    if _eng.is_device(engine):
+        return _device_reports([engine], None, age_group, n_groups)[0]
     nr_ages = engine.config.nr_ages
     table, ng = _group_table(age_group, nr_ages)
-    ng = max(ng, int(n_groups or 0))
-    if not _eng.is_device(engine):
-        hot, inf, cnt, counters = _host_fields(engine)
-        age_start = np.asarray(engine.config.age_start, dtype=np.int64)
-        r = report_numpy(hot, inf, cnt, age_start, table[:nr_ages], _day_depth(counters))
-        if r.unconverged:
-            r = report_numpy(hot, inf, cnt, age_start, table[:nr_ages], engine.config.n_agents)
-        r.n_groups = ng
-        return r
-    words = _device_report(engine, table, ng, 0)
-    if words[SCALARS + SCALAR_NAMES.index('unconverged')]:
-        words = _device_report(engine, table, ng, engine.config.n_agents)
-    return TransmissionReport(words, ng)
+    hot, inf, cnt, counters = _rep.host_state(engine)
+    age_start = np.asarray(engine.config.age_start, dtype=np.int64)
+    take = lambda depth: report_numpy(hot, inf, cnt, age_start, table[:nr_ages], depth or _rep.day_depth(counters)).words[None]
+    return TransmissionReport(_rep.with_deep_pass(take, _UNCONVERGED, engine.config.n_agents)[0], max(ng, int(n_groups or 0)))
 
 
 def report_group(group, age_group, n_groups=None):
     """The reports of every member of an engine group: one launch per pass on the device, report_engine per member
     otherwise."""
-    e0 = group.engines[0]
-    if not _eng.is_device(e0):
+    if not _eng.is_device(group.engines[0]):
         return [report_engine(e, age_group, n_groups) for e in group.engines]
-    for e in group.engines:
-        _check_unsharded(e.config)
-    f = _tx_f(e0)
-    table, ng = _group_table(age_group, e0.config.nr_ages)
-    ng = max(ng, int(n_groups or 0))
-    torch = e0.alloc.torch
-    dev = e0.alloc.device
-    K = len(group.engines)
-    scratch = [torch.empty(scratch_bytes(e.config.n_agents), dtype=torch.uint8, device=dev) for e in group.engines]
-    ptrs = (ctypes.c_void_p * K)(*[s.data_ptr() for s in scratch])
-    rep = torch.empty(K * REPORT_WORDS, dtype=torch.int64, device=dev)
-    e0._check(f['group_tx_report'](group._h, table.ctypes.data, ng, 0, ptrs, rep.data_ptr(), e0.alloc.stream()), 'group_tx_report')
-    _eng.mark_stale(group.engines)
-    del scratch
-    words = rep.cpu().numpy().view(np.uint64).reshape(K, REPORT_WORDS)
-    out = []
-    for k, e in enumerate(group.engines):
-        if words[k, SCALARS + SCALAR_NAMES.index('unconverged')]:
-            out.append(TransmissionReport(_device_report(e, table, ng, e.config.n_agents), ng))
-        else:
-            out.append(TransmissionReport(words[k].copy(), ng))
-    return out
+    return _device_reports(group.engines, group, age_group, n_groups)
 
 
 def report_from_snapshot(snap, age_counts, age_group=None):
@@ -286,23 +178,16 @@ def report_from_snapshot(snap, age_counts, age_group=None):
     table = default_age_groups(len(ages))[0] if age_group is None else age_group
     table, ng = _group_table(table, len(ages))
     counters = words[_snap.HEADER_WORDS:_snap.HEADER_WORDS + _eng.COUNTER_WORDS]
-    r = report_numpy(hot, inf, cnt, age_start, table[:len(ages)], _day_depth(counters))
-    if r.unconverged:
-        r = report_numpy(hot, inf, cnt, age_start, table[:len(ages)], n)
-    r.n_groups = ng
-    return r
+    take = lambda depth: report_numpy(hot, inf, cnt, age_start, table[:len(ages)], depth or _rep.day_depth(counters)).words[None]
+    return TransmissionReport(_rep.with_deep_pass(take, _UNCONVERGED, n)[0], ng)
 
 
-class TransmissionReport:
+class TransmissionReport(_rep.Report):
     """One report: the words of include/reina_transmission.h as named arrays, plus the statistics derived from them."""
+    SCALARS, SCALAR_NAMES = SCALARS, SCALAR_NAMES
 
     def __init__(self, words, n_groups=MAX_GROUPS, group_labels=None):
-        w = np.asarray(words, dtype=np.uint64).ravel()
-        if len(w) != REPORT_WORDS:
-            raise ValueError('a transmission report has %d words' % REPORT_WORDS)
-        self.words = w
-        self.n_groups = int(n_groups)
-        self.group_labels = list(group_labels) if group_labels is not None else None
+        w = self._take(words, REPORT_WORDS, 'a transmission report has %d words' % REPORT_WORDS, n_groups, group_labels)
         self.offspring = w[OFFSPRING:OFFSPRING_SUM].reshape(VARIANTS, SEVERITIES, OUTCOMES, 2, BINS)
         self.offspring_sum = w[OFFSPRING_SUM:OFFSPRING_SUMSQ].reshape(VARIANTS, OUTCOMES)
         self.offspring_sumsq = w[OFFSPRING_SUMSQ:MATRIX].reshape(VARIANTS, OUTCOMES)
@@ -310,13 +195,6 @@ class TransmissionReport:
         self.generations = w[GENERATION:CLUSTERS].reshape(VARIANTS, GENERATIONS)
         self.clusters = w[CLUSTERS:CLUSTER_AGENTS]
         self.cluster_agents = w[CLUSTER_AGENTS:SCALARS]
-        for k, name in enumerate(SCALAR_NAMES):
-            setattr(self, name, int(w[SCALARS + k]))
-        if self.largest_root == (1 << 64) - 1:
-            self.largest_root = -1
-
-    def __eq__(self, other):
-        return isinstance(other, TransmissionReport) and np.array_equal(self.words, other.words)
 
     def __repr__(self):
         return 'TransmissionReport(infected=%d, roots=%d, linked=%d, max_generation=%d, largest_cluster=%d)' % (
@@ -377,7 +255,7 @@ class TransmissionReport:
         import pandas as pd
         m = self.matrix if variant is None else self.matrix[int(variant):int(variant) + 1]
         m = m.sum(axis=0, dtype=np.uint64)[:self.n_groups, :self.n_groups].astype(np.int64)
-        labels = self.group_labels or [str(k) for k in range(self.n_groups)]
+        labels = self._groups()
         return pd.DataFrame(m, index=pd.Index(labels, name='infector'), columns=pd.Index(labels, name='infectee'))
 
     def to_dict(self):

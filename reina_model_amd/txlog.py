@@ -28,7 +28,8 @@ import ctypes
 import numpy as np
 
 from . import engine as _eng
-from .transmission import _group_table
+from . import reports as _rep
+from .reports import _group_table
 
 TXLOG_VERSION = 1              # include/reina_txlog.h: REINA_TXLOG_VERSION
 NONE, BEFORE = 0xFFFF, 0xFFFE
@@ -68,6 +69,15 @@ def cohort_offset(n_days):
 def report_words(n_days):
     """include/reina_txlog.h: REINA_TXLOG_REPORT_WORDS"""
     return FIXED_WORDS + int(n_days) * DAY_WORDS
+
+
+def check_n_days(n_days):
+    """the one statement of a report's range of days; every route takes it before it builds or launches anything"""
+    if not 1 <= int(n_days) <= _eng.MAX_DAYS:
+        raise ValueError('n_days must be in [1, %d]' % _eng.MAX_DAYS)
+    return int(n_days)
+
+
 _vp, _u32 = ctypes.c_void_p, ctypes.c_uint32
 _TXLOG_ARGTYPES = {'txlog_create': [_vp, _vp, _vp], 'group_txlog_create': [_vp, _vp, _vp], 'txlog_destroy': [_vp],
                    'txlog_record_day': [_vp, _u32, _vp],
@@ -109,19 +119,12 @@ def report_numpy(hot, infector, n_infected, log, age_start, age_group, n_days):
     int32[N] (the cold record's fields); log: uint32[N]; age_start: first agent of each age ([A] = N, padded with N);
     age_group: group of each age (< MAX_GROUPS); n_days: the dated tables hold the days [0, n_days)."""
     hot = np.asarray(hot).view(np.uint32).ravel()
-    n = len(hot)
-    n_days = int(n_days)
-    if not 1 <= n_days <= _eng.MAX_DAYS:
-        raise ValueError('n_days must be in [1, %d]' % _eng.MAX_DAYS)
-    src = np.asarray(infector).view(np.int32).ravel().astype(np.int64)
+    n_days = check_n_days(n_days)
     cnt = np.asarray(n_infected).view(np.uint32).ravel().astype(np.uint64)
     log = np.asarray(log, dtype=np.uint32).ravel()
-    age_start = np.asarray(age_start, dtype=np.int64).ravel()
-    nr_ages = min(len(np.asarray(age_group).ravel()), _eng.MAX_AGES, len(age_start) - 1)
-    table, n_groups = _group_table(age_group, nr_ages)
+    table, n_groups, _, age_of = _rep.age_lookup(age_start, age_group)
     words = np.zeros(report_words(n_days), dtype=np.uint64)
-    state = hot & 7
-    idx = np.flatnonzero(state != 0)
+    _, idx, s, _, linked, bad = _rep.links(hot, infector)
     w = hot[idx]
     v = ((w >> 8) & 3).astype(np.int64)
     t = (log[idx] & 0xFFFF).astype(np.int64)
@@ -133,12 +136,6 @@ def report_numpy(hot, infector, n_infected, log, age_start, age_group, n_days):
         words[offset:offset + VARIANTS * bins] = np.bincount(cell, minlength=VARIANTS * bins).astype(np.uint64)
 
     hist(INCUBATION, INCUBATION_BINS, tk & ok, (o - t)[tk & ok])
-    s = src[idx]
-    root = s == -1
-    in_range = (s >= 0) & (s < n) & (s != idx)
-    linked = np.zeros(len(idx), dtype=bool)
-    linked[in_range] = state[s[in_range]] != 0
-    bad = ~root & ~linked
     sl = np.zeros(len(idx), dtype=np.uint32)
     sl[linked] = log[s[linked]]
     ts, os_ = (sl & 0xFFFF).astype(np.int64), (sl >> 16).astype(np.int64)
@@ -150,8 +147,7 @@ def report_numpy(hot, infector, n_infected, log, age_start, age_group, n_days):
     phase = np.where(tk & osk, np.where(t < os_, 0, 1), np.where(tk & (os_ == NONE), 2, 3))
     hist(LINK_PHASE, PHASES, linked, phase[linked])
 
-    ages = np.clip(np.searchsorted(age_start[:nr_ages + 1], idx, side='right') - 1, 0, nr_ages - 1)
-    g = table[ages].astype(np.int64)
+    g = table[age_of(idx)].astype(np.int64)
     inr = tk & (t < n_days)
     a, b, c = incidence_offset(n_days), onsets_offset(n_days), cohort_offset(n_days)
     words[a:b] = np.bincount((t[inr] * VARIANTS + v[inr]) * MAX_GROUPS + g[inr], minlength=b - a).astype(np.uint64)
@@ -198,19 +194,19 @@ class _Intervals:
         n = self.total()
         if not n:
             return None
-        return int(self.values[np.searchsorted(np.cumsum(self.counts), q * n, side='left')])
+        if not 0 <= q <= 1:
+            raise ValueError('quantile: q must be in [0, 1]')
+        return int(self.values[np.argmax(np.cumsum(self.counts) >= q * n)])   # (the first value the cumulated counts reach q * n at)
 
 
-class LogReport:
+class LogReport(_rep.Report):
     """One report: the words of include/reina_txlog.h as named arrays, plus what is derived from them."""
+    SCALARS, SCALAR_NAMES, IDENTITY = SCALARS, SCALAR_NAMES, ('n_days',)
 
     def __init__(self, words, n_days, n_groups=MAX_GROUPS, group_labels=None, start_date=None):
-        w = np.asarray(words, dtype=np.uint64).ravel()
-        n_days = int(n_days)
-        if len(w) != report_words(n_days):
-            raise ValueError('a log report of %d days has %d words' % (n_days, report_words(n_days)))
-        self.words, self.n_days, self.n_groups = w, n_days, int(n_groups)
-        self.group_labels = list(group_labels) if group_labels is not None else None
+        self.n_days = n_days = int(n_days)
+        w = self._take(words, report_words(n_days), 'a log report of %d days has %d words' % (n_days, report_words(n_days)),
+                       n_groups, group_labels)
         self.start_date = start_date
         self.incubation = w[INCUBATION:GENERATION].reshape(VARIANTS, INCUBATION_BINS)
         self.generation = w[GENERATION:SERIAL].reshape(VARIANTS, GENERATION_BINS)
@@ -221,13 +217,8 @@ class LogReport:
         self.incidence = w[a:b].reshape(n_days, VARIANTS, MAX_GROUPS)
         self.onsets = w[b:c].reshape(n_days, VARIANTS)
         self.cohort = w[c:].reshape(n_days, VARIANTS, COHORT_FIELDS)
-        for k, name in enumerate(SCALAR_NAMES):
-            setattr(self, name, int(w[SCALARS + k]))
         if self.dated == 0:
             self.first_day = self.last_day = -1
-
-    def __eq__(self, other):
-        return isinstance(other, LogReport) and self.n_days == other.n_days and np.array_equal(self.words, other.words)
 
     def __repr__(self):
         return 'LogReport(days=%d, infected=%d, dated=%d, before=%d, links=%d)' % (self.n_days, self.infected, self.dated, self.before, self.links)
@@ -249,8 +240,7 @@ class LogReport:
         """infections by date of infection (rows) and age group (columns), of one variant or all"""
         import pandas as pd
         m = self._v(self.incidence, variant)[:, :self.n_groups].astype(np.int64)
-        labels = self.group_labels or [str(k) for k in range(self.n_groups)]
-        return pd.DataFrame(m, index=self._dates(), columns=pd.Index(labels, name='age_group'))
+        return pd.DataFrame(m, index=self._dates(), columns=pd.Index(self._groups(), name='age_group'))
 
     def onset_series(self, variant=None):
         import pandas as pd
@@ -304,9 +294,7 @@ class DeviceLog:
     """The library's log of one engine, or of the members of an engine group (include/reina_txlog.h)."""
 
     def __init__(self, engine, group=None):
-        f = engine.txlog_f
-        if f is None:
-            raise _eng.EngineError('the engine library has no transmission-log entry points (include/reina_txlog.h)')
+        f = _rep.entry_points(engine, 'txlog_f', 'transmission-log', 'reina_txlog.h')
         self.f, self.engine, self.group = f, engine, group
         self.members = 1 if group is None else len(group.engines)
         self._h = ctypes.c_void_p()
@@ -326,8 +314,12 @@ class DeviceLog:
         except Exception:
             pass
 
+    @property
+    def engines(self):
+        return [self.engine] if self.group is None else self.group.engines
+
     def _touch(self):
-        _eng.mark_stale([self.engine] if self.group is None else self.group.engines)
+        _eng.mark_stale(self.engines)
 
     def record_day(self, day):
         self.engine._check(self.f['txlog_record_day'](self._h, int(day), self.engine.alloc.stream()), 'txlog_record_day')
@@ -354,12 +346,9 @@ class DeviceLog:
 
     def report_words(self, table, n_groups, n_days):
         """[members, report_words(n_days)] uint64: one launch for all members"""
-        torch = self.engine.alloc.torch
-        rep = torch.empty(self.members * report_words(n_days), dtype=torch.int64, device=self.engine.alloc.device)
         name = 'txlog_report' if self.group is None else 'group_txlog_report'
-        self.engine._check(self.f[name](self._h, table.ctypes.data, int(n_groups), int(n_days), rep.data_ptr(), self.engine.alloc.stream()), name)
-        self._touch()
-        return rep.cpu().numpy().view(np.uint64).reshape(self.members, report_words(n_days))
+        return _rep.device_words(self.engine, self.f, name, (self._h, table.ctypes.data, int(n_groups), int(n_days)), self.members,
+                                 report_words(n_days), stale=self.engines, group=self.group is not None)
 
 
 class TransmissionLog:
@@ -414,18 +403,11 @@ class TransmissionLog:
     def report(self, age_groups=None, n_days=None):
         """LogReport of the days [0, n_days) (default: the days run so far)"""
         ctx = self.ctx
-        table, labels = ctx._tx_groups(age_groups)
-        n_days = max(int(ctx.day), 1) if n_days is None else int(n_days)
-        if not 1 <= n_days <= _eng.MAX_DAYS:
-            raise ValueError('n_days must be in [1, %d]' % _eng.MAX_DAYS)
         if self.device is not None and self.device.group is None:
-            t8, ng = _group_table(table, ctx.nr_ages)
-            w = self.device.report_words(t8, max(ng, len(labels)), n_days)[0]
-        else:
-            e = ctx.engine
-            n = e.config.n_agents
-            cold = _host_array(e.tensors['cold']).view(np.uint32).reshape(n, _eng.COLD_WORDS)
-            w = report_numpy(_host_array(e.tensors['hot']), cold[:, 2], cold[:, 3], self.words(), ctx.age_start, table, n_days).words
+            return report_group(self.device, [ctx], age_groups, n_days)[0]
+        table, labels = ctx._tx_groups(age_groups)
+        n_days = check_n_days(max(int(ctx.day), 1) if n_days is None else n_days)
+        w = report_numpy(*_rep.host_state(ctx.engine)[:3], self.words(), ctx.age_start, table, n_days).words
         return LogReport(w, n_days, len(labels), labels, ctx.start_date)
 
     def lineage_report(self, period=7, n_periods=None, age_groups=None):
@@ -439,24 +421,21 @@ class TransmissionLog:
     def line_list(self):
         """One row per infected agent (a pandas DataFrame, built on the host from the hot words, the cold records and the log):
         agent, age, infector (-1: an import or the initial condition), infector_age (-1 without one), infection_day and
-        onset_day (-1 NONE, -2 BEFORE), variant, severity, state, detected, n_infected."""
+        onset_day (-1 NONE, -2 BEFORE), variant, severity, state, detected, n_infected.  The infector column holds every
+        infector word that is in range, that of a bad link (a self-link, a link to a susceptible agent) included: a row has an
+        infector when its word names an agent, not only when reports.links calls it linked."""
         import pandas as pd
-        e = self.ctx.engine
-        n = e.config.n_agents
-        hot = _host_array(e.tensors['hot']).view(np.uint32)
-        cold = _host_array(e.tensors['cold']).view(np.int32).reshape(n, _eng.COLD_WORDS)
+        hot, infector, n_infected, _ = _rep.host_state(self.ctx.engine)
         log = self.words()
-        idx = np.flatnonzero(hot & 7)
-        starts = np.asarray(self.ctx.age_start[:self.ctx.nr_ages + 1])
-        age = lambda i: np.clip(np.searchsorted(starts, i, side='right') - 1, 0, self.ctx.nr_ages - 1)
-        src = cold[idx, 2].astype(np.int64)
-        has = (src >= 0) & (src < n)
+        _, idx, src, _, _, _ = _rep.links(hot, infector)
+        age = _rep.age_lookup(self.ctx.age_start, np.zeros(self.ctx.nr_ages, dtype=np.int64))[3]   # (the ages alone: no groups here)
+        has = (src >= 0) & (src < len(hot))
         w = hot[idx]
         return pd.DataFrame(dict(
             agent=idx, age=age(idx), infector=np.where(has, src, -1), infector_age=np.where(has, age(np.where(has, src, 0)), -1),
             infection_day=_signed(log[idx] & 0xFFFF), onset_day=_signed(log[idx] >> 16), variant=((w >> 8) & 3).astype(np.int64),
             severity=np.minimum((w >> 3) & 7, 4).astype(np.int64), state=(w & 7).astype(np.int64), detected=(w & 0x40) != 0,
-            n_infected=cold[idx, 3].astype(np.int64)))
+            n_infected=n_infected.view(np.int32)[idx].astype(np.int64)))
 
 
 def _signed(half):
@@ -494,10 +473,10 @@ def run_host_driven(ctx, days, record_history=True, on_day=None):
 
 
 def report_group(device_log, contexts, age_groups=None, n_days=None):
-    """The reports of every member of a logged group: one launch for all members."""
+    """The reports of every member of a logged group (or of the one engine of a device log): one launch for all members."""
     c0 = contexts[0]
     table, labels = c0._tx_groups(age_groups)
-    n_days = max(int(c0.day), 1) if n_days is None else int(n_days)
+    n_days = check_n_days(max(int(c0.day), 1) if n_days is None else n_days)
     t8, ng = _group_table(table, c0.nr_ages)
     w = device_log.report_words(t8, max(ng, len(labels)), n_days)
-    return [LogReport(w[m].copy(), n_days, len(labels), labels, c.start_date) for m, c in enumerate(contexts)]
+    return [LogReport(r, n_days, len(labels), labels, c.start_date) for r, c in zip(_rep.member_rows(w), contexts)]

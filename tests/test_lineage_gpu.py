@@ -156,6 +156,41 @@ def test_a_logged_group_is_reported_by_one_launch_per_pass():
     assert ctxs[3].transmission_log.lineage_report(7, 18) == reps[3]
 
 
+def test_a_group_takes_its_second_pass_as_a_group_and_replaces_only_the_deep_member():
+    """three members of 513 agents; only member 1 holds a chain deeper than its day + 1.  Every member's words are report_numpy's
+    with max_depth = n_agents, and those of members 0 and 2 are the words of their first pass.  `rounds` is one of the words, so
+    both can hold only if the first pass of members 0 and 2 runs the rounds of the second: their day + 1 is 513.  The words
+    then cannot tell a kept row from a replaced one; what pins the mechanism is the list of launches -- the group entry point
+    twice, no member on its own"""
+    n = 513
+    ctxs = [snap_util.make_context(n) for _ in range(3)]
+    states = [tu.forest_state(n, 'random'), tu.forest_state(n, 'chain'), tu.forest_state(n, 'bad_links', seed=2)]
+    days = (n - 1, 3, n - 1)
+    group = eng.EngineGroup([c.engine for c in ctxs])
+    glog = txl.DeviceLog(ctxs[0].engine, group=group)
+    try:
+        for m, (c, (hot, inf, cnt, log), day) in enumerate(zip(ctxs, states, days)):
+            tx_util.put_forest(c, hot, inf, cnt, day=day)
+            c.transmission_log = txl.TransmissionLog(c, device=glog, member=m)
+            c.transmission_log.set_words(log)
+        f, launches = ctxs[0].engine.lineage_f, []
+        for name in ('lineage_report', 'group_lineage_report'):
+            f[name] = (lambda real, name: lambda *args: (launches.append(name), real(*args))[1])(f[name], name)
+        g = tx_util.groups('fine')
+        reps = ensemble.lineage_reports(ctxs, 7, 43, g)
+    finally:
+        glog.close()
+        group.close()
+    assert launches == ['group_lineage_report'] * 2                  # one launch per pass, no member on its own
+    spec = lambda m, depth: lin.report_numpy(*states[m], ctxs[m].age_start, g, 7, 43, depth)
+    for m in range(3):
+        lu.assert_words(reps[m].words, spec(m, n).words)
+        assert reps[m].unconverged == 0
+    for m in (0, 2):
+        lu.assert_words(reps[m].words, spec(m, days[m] + 1).words)
+    assert spec(1, days[1] + 1).unconverged > 0 and reps[1].largest_tree == n and reps[2].bad_links > 0
+
+
 # ---------------------------------------------------------------------------------------------- 11. a report changes nothing
 
 def test_report_between_two_days_changes_nothing():

@@ -143,6 +143,40 @@ def test_group_report_equals_single_reports():
     assert reps[0].max_generation == 2999 and reps[0].unconverged == 0
 
 
+def _count_launches(f, names):
+    """wrap the entries `names` of an engine's table of entry points; returns the list their names are appended to"""
+    launches = []
+    for name in names:
+        f[name] = (lambda real, name: lambda *args: (launches.append(name), real(*args))[1])(f[name], name)
+    return launches
+
+
+def test_a_group_takes_its_second_pass_as_a_group_and_replaces_only_the_deep_member():
+    """three members of 513 agents; only member 1 holds a chain deeper than its day + 1.  Every member's words are report_numpy's
+    with max_depth = n_agents, and those of members 0 and 2 are the words of their first pass.  `rounds` is one of the words, so
+    both can hold only if the first pass of members 0 and 2 runs the rounds of the second: their day + 1 is 513.  The words
+    then cannot tell a kept row from a replaced one; what pins the mechanism is the list of launches -- the group entry point
+    twice, no member on its own"""
+    n = 513
+    ctxs = [snap_util.make_context(n) for _ in range(3)]
+    states = [tx_util.forest(n, 'random'), tx_util.forest(n, 'chain'), tx_util.forest(n, 'bad_links', seed=2)]
+    days = (n - 1, 3, n - 1)
+    for c, state, day in zip(ctxs, states, days):
+        tx_util.put_forest(c, *state, day=day)
+    launches = _count_launches(ctxs[0].engine.tx_f, ('tx_report', 'group_tx_report'))
+    g = tx_util.groups('fine')
+    reps = ensemble.transmission_reports(ctxs, g)
+    assert launches == ['group_tx_report'] * 2                       # one launch per pass, no member on its own
+    age_start = np.asarray(ctxs[0].engine.config.age_start)
+    for m in range(3):
+        _assert_same(reps[m], tx.report_numpy(*states[m], age_start, g, n))
+        assert reps[m].unconverged == 0
+    for m in (0, 2):
+        _assert_same(reps[m], tx.report_numpy(*states[m], age_start, g, days[m] + 1))
+    assert tx.report_numpy(*states[1], age_start, g, days[1] + 1).unconverged > 0 and reps[1].max_generation == n - 1
+    assert reps[2].bad_links > 0
+
+
 def test_report_between_days_does_not_change_the_gpu_continuation():
     v = copy.deepcopy(VARIABLE_DEFAULTS)
     ages = datasets.get_population_for_area('HUS')
