@@ -1460,3 +1460,6 @@ int reina_profile_read(reina_engine_t *e, double *scan_ms_total, uint64_t *scan_
 
 // lineage reports: mixing by period and trees by seeding period (include/reina_lineage.h): kernels and entry points
 #include "k_lineage.inc"
+
+// ensemble summaries: bands, sums, peaks and exceedance of the members' histories (include/reina_summary.h): kernels and entry point
+#include "k_summary.inc"

@@ -48,6 +48,11 @@ class History:
             return self.base + ROW * issued
         return [self.base + ROW * (m * self.days + issued) for m in range(self.members)]
 
+    def rows(self):
+        """a group's rows where they are, [members, days, COUNTER_WORDS]: the device tensor of a device group (nothing is
+        read back, nothing waited for), the host array of a host-memory one"""
+        return self.buf.reshape(self.members, self.days, _eng.COUNTER_WORDS)
+
     def to_host(self):
         """[days, COUNTER_WORDS] ([members, days, COUNTER_WORDS] of a group) or None; waits for the run, and for a Context
         raises SimulationFailed when the run has failed"""

@@ -25,7 +25,7 @@ from .dayrun import History, replay_plan
 from .filtering import particle_filter  # noqa: F401  (conditioned ensembles: reina_model_amd/filtering.py)
 
 
-def run_group_plan(contexts, plan, record_history=True, member_plans=None, group=None, policy=None, txlog=False):
+def run_group_plan(contexts, plan, record_history=True, member_plans=None, group=None, policy=None, txlog=False, summary=None):
     """Execute `plan` (Context.make_plan) for all `contexts` as one engine group.  Returns
     history[len(contexts), days, COUNTER_WORDS] (host) or None.
 
@@ -43,10 +43,17 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
     `txlog`: every member keeps a dated transmission log (reina_model_amd/txlog.py), recorded by one launch a day for the
     whole group; the members' logs end up on `contexts[m].transmission_log` and share the group's device log, which lives as
     long as they do (and keeps a group made for the run open).  A later call with the same `group` continues them; members that keep logs already are continued
-    whatever `txlog` says.  Not together with a policy."""
+    whatever `txlog` says.  Not together with a policy.
+
+    `summary` (summary.SummarySpec): an EnsembleSummary (quantile bands, peaks, exceedance: reina_model_amd/summary.py) is
+    returned in place of the history, computed where the rows are: a device group's rows are never read back.  The members'
+    final counters are checked as always."""
     from . import engine as _eng
     from . import policy as _pol
     from . import txlog as _txl
+    if summary is not None:
+        from . import summary as _summ
+        _summ.check_group(summary, contexts, plan, record_history)
     logged = [c.transmission_log is not None for c in contexts]
     if (txlog or any(logged)) and policy is not None:
         raise ValueError('run_group_plan: a transmission log and a policy cannot be combined')
@@ -119,7 +126,7 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
         else:
             c.mobility_history = (member_plans[m] if member_plans is not None else plan)['mobility_history']
         c.day = start_day + days
-    out = hist.to_host()
+    out = hist.to_host() if summary is None else _summ.of_group(summary, hist.rows(), contexts, start_day)
     _t('history on the host')
     torch = getattr(a, 'torch', None)
     if torch is not None:
@@ -190,11 +197,13 @@ def run_ensemble_distributed(variables, seeds, days, group=None, concurrent=64, 
 
 
 def run_ensemble(variables, seeds, days, age_counts=None, device='cuda:0', threads=8, concurrent=None,
-                 interventions=None, batched=True, engine_factory=None, ipc='auto'):
+                 interventions=None, batched=True, engine_factory=None, ipc='auto', summary=None):
     """Run one simulation per seed for `days` days. Returns history[len(seeds), days, COUNTER_WORDS]
     (row d = counters before day d, as Context.run). `concurrent` bounds how many members hold HBM
     state at once (default: all).  `ipc`: the initial population condition of every member; 'auto' = the
-    one simulate_individuals applies for these variables (calc/simulation.py:152), None = none."""
+    one simulate_individuals applies for these variables (calc/simulation.py:152), None = none.
+    `summary` (summary.SummarySpec): the EnsembleSummary of all seeds instead of the history -- the chunks' histories stay on
+    the device until the last has run and are summarised in one call; the threaded route summarises on the host."""
     import torch
     seeds = list(seeds)
     concurrent = len(seeds) if concurrent is None else max(1, int(concurrent))
@@ -202,14 +211,20 @@ def run_ensemble(variables, seeds, days, age_counts=None, device='cuda:0', threa
         planner = simulation.make_context(variables, age_counts=age_counts, seed=seeds[0], device=device,
                                           interventions=interventions, engine_factory=engine_factory, ipc=ipc)
         plan = planner.make_plan(days)
+        pending = None
+        if summary is not None:
+            from . import summary as _summ
+            pending = _summ.Pending(summary, planner, plan['start_day'])
         del planner
         outs = []
         for start in range(0, len(seeds), concurrent):
             ctxs = [simulation.make_context(variables, age_counts=age_counts, seed=sd, device=device,
                                             interventions=interventions, engine_factory=engine_factory, ipc=ipc)
                     for sd in seeds[start:start + concurrent]]
-            outs.append(run_group_plan(ctxs, plan))
+            outs.append(run_group_plan(ctxs, plan, summary=pending))
             del ctxs
+        if pending is not None:
+            return pending.finish(members=seeds)
         return np.concatenate(outs)
     out = [None] * len(seeds)
     dev = torch.device(device)
@@ -218,6 +233,10 @@ def run_ensemble(variables, seeds, days, age_counts=None, device='cuda:0', threa
     planner = simulation.make_context(variables, age_counts=age_counts, seed=seeds[0], device=device,
                                       interventions=interventions, ipc=ipc)
     plan = planner.make_plan(days)
+    pending = None
+    if summary is not None:
+        from . import summary as _summ
+        pending = _summ.Pending(summary, planner, plan['start_day'])
     del planner
 
     def work(k):
@@ -237,14 +256,18 @@ def run_ensemble(variables, seeds, days, age_counts=None, device='cuda:0', threa
         batch = range(start, min(len(seeds), start + concurrent))
         with ThreadPoolExecutor(max_workers=min(threads, len(batch))) as pool:
             list(pool.map(work, batch))
+    if pending is not None:
+        pending.add(np.stack(out))
+        return pending.finish(members=seeds)
     return np.stack(out)
 
 
 def run_policy_ensemble(variables, seeds, days, policy, age_counts=None, device='cuda:0', engine_factory=None, ipc='auto',
-                        interventions=None):
+                        interventions=None, summary=None):
     """One simulation per seed for `days` days, every member reacting to its own counters under `policy` (policy.Policy), all
     as ONE engine group.  Returns (history[K, days, COUNTER_WORDS], levels[K, days], contexts).  An engine library without the
-    policy entry points runs the members one after the other by policy.run_host_driven."""
+    policy entry points runs the members one after the other by policy.run_host_driven.  `summary` (summary.SummarySpec): the
+    EnsembleSummary in place of the history."""
     from . import policy as _pol
     seeds = list(seeds)
     mk = lambda sd: simulation.make_context(variables, age_counts=age_counts, seed=sd, device=device, interventions=interventions,
@@ -252,16 +275,19 @@ def run_policy_ensemble(variables, seeds, days, policy, age_counts=None, device=
     ctxs = [mk(sd) for sd in seeds]
     if ctxs[0].engine.policy_f is None:
         hist = np.stack([_pol.run_host_driven(c, policy, days) for c in ctxs])
+        if summary is not None:
+            from . import summary as _summ
+            hist = _summ.summarise(hist, ctxs[0].nr_ages, summary, ctx=ctxs[0], members=seeds)
     else:
         planner = mk(seeds[0])
         plan = planner.make_plan(days, policy=policy)
         del planner
-        hist = run_group_plan(ctxs, plan, policy=policy)
+        hist = run_group_plan(ctxs, plan, policy=policy, summary=summary)
     return hist, np.stack([c.policy_levels for c in ctxs]), ctxs
 
 
 def run_branches(snap, variables, seeds, days, member_variables=None, age_counts=None, device='cuda:0', engine_factory=None,
-                 interventions=None, policy=None):
+                 interventions=None, policy=None, summary=None):
     """Conditional ensemble: K = len(seeds) futures of ONE realised past.  Every member is a Context of `variables` (or of
     member_variables[m]) restored from `snap` (snapshot.Snapshot) -- on the device all K by one launch
     (reina_group_snap_unpack) -- with its own seed, then `days` days are run as one engine group (run_group_plan).
@@ -269,7 +295,8 @@ def run_branches(snap, variables, seeds, days, member_variables=None, age_counts
     interventions.  `interventions`: intervention tuples of every member instead of its variables' scenario (make_context).
     `policy` (policy.Policy): every future reacts to its own course from the snapshot's day on (levels in
     contexts[m].policy_levels); not together with member_variables.
-    Returns (history[K, days, COUNTER_WORDS], contexts)."""
+    Returns (history[K, days, COUNTER_WORDS], contexts); with `summary` (summary.SummarySpec) the EnsembleSummary of the futures
+    in place of the history."""
     from . import engine as _eng
     from . import snapshot as _snap
     if policy is not None and member_variables is not None:
@@ -305,7 +332,7 @@ def run_branches(snap, variables, seeds, days, member_variables=None, age_counts
         for c in ctxs:
             c.engine.upload_contact_tables(*c._packed_tables_for_restore(snap.state))
         member_plans = plans if member_variables is not None else None
-        hist = run_group_plan(ctxs, plans[0], member_plans=member_plans, group=group, policy=policy)
+        hist = run_group_plan(ctxs, plans[0], member_plans=member_plans, group=group, policy=policy, summary=summary)
     finally:
         group.close()
     return hist, ctxs

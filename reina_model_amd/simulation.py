@@ -304,12 +304,15 @@ def simulate_monte_carlo(seed, variables=None, device='cuda:0', engine_factory=N
 
 
 def run_monte_carlo(scenario_name, seeds=range(1000), device='cuda:0', group_size=64, days=None, write_csv=True,
-                    age_counts=None, engine_factory=None, variables=None, ipc='auto'):
+                    age_counts=None, engine_factory=None, variables=None, ipc='auto', summary=None):
     """calc/simulation.py:362-385 with the seeds stepped as engine groups on one GPU instead of a
     process pool: one DataFrame with every run's per-date rows, columns as simulate_individuals
     plus 'run' and 'scenario'; written to reina_<scenario>.csv like the reference.  Every run starts from
     the scenario's initial population condition, as the reference's do (run_monte_carlo ->
-    simulate_monte_carlo -> simulate_individuals, calc/simulation.py:152); `ipc` overrides it."""
+    simulate_monte_carlo -> simulate_individuals, calc/simulation.py:152); `ipc` overrides it.
+    `summary` (summary.SummarySpec): the EnsembleSummary of all seeds instead of the frame (quantile bands, peaks, exceedance:
+    reina_model_amd/summary.py) -- no history is read back, no frame per run is built; with write_csv its frame() goes to
+    reina_<scenario>_bands.csv."""
     import pandas as pd
     from . import ensemble
     from .scenarios import scenario_variables
@@ -317,12 +320,20 @@ def run_monte_carlo(scenario_name, seeds=range(1000), device='cuda:0', group_siz
     days = v['simulation_days'] if days is None else days
     seeds = list(seeds)
     dfs = []
+    pending = None
     for start in range(0, len(seeds), group_size):
         part = seeds[start:start + group_size]
         planner = make_context(v, age_counts=age_counts, seed=part[0], device=device, engine_factory=engine_factory, ipc=ipc)
         plan = planner.make_plan(days)
         members = [make_context(v, age_counts=age_counts, seed=sd, device=device, engine_factory=engine_factory, ipc=ipc)
                    for sd in part]
+        if summary is not None:
+            if pending is None:
+                from . import summary as _summ
+                pending = _summ.Pending(summary, planner, plan['start_day'])
+            ensemble.run_group_plan(members, plan, summary=pending)
+            del members, planner
+            continue
         t0 = time.perf_counter()
         hist = ensemble.run_group_plan(members, plan)
         ms_per_day = (time.perf_counter() - t0) * 1000 / days / len(part)
@@ -332,6 +343,11 @@ def run_monte_carlo(scenario_name, seeds=range(1000), device='cuda:0', group_siz
             df['run'] = sd
             dfs.append(df)
         del members, planner
+    if summary is not None:
+        out = pending.finish(members=seeds)
+        if write_csv:
+            out.frame().to_csv('reina_%s_bands.csv' % scenario_name)
+        return out
     df = pd.concat(dfs)
     df.index.name = 'date'
     df = df.reset_index()
