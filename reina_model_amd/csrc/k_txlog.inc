@@ -68,6 +68,24 @@ __global__ __launch_bounds__(TXL_THREADS) void k_txlog_begin(const MemberRef *M_
     }
 }
 
+// the day's update of one infected agent's log word, in both forms (the header comment: by_hot): shared by k_txlog_day and
+// k_course_day (k_course.inc), so that the two cannot disagree.  d8 / o8: day and day + 1 as bits 24-31 hold them.
+__device__ __forceinline__ void txl_day_update(GAS uint32_t *L, uint32_t i, uint32_t w, uint32_t day, uint32_t d8, uint32_t o8, uint32_t by_hot) {
+    const uint32_t st = RH_STATE(w);
+    if (by_hot) {
+        if (st == RS_INCUBATION && (w >> 24) == d8)
+            L[i] = TXL_NONE << 16 | day;
+        else if (st == RS_ILLNESS && (w >> 24) == o8)
+            reinterpret_cast<GAS uint16_t *>(L)[2u * i + 1u] = (uint16_t)day;
+    } else {
+        const uint32_t lw = L[i];
+        uint32_t nw = lw;
+        if ((lw & 0xFFFFu) == TXL_NONE) nw = (nw & 0xFFFF0000u) | day;
+        if ((lw >> 16) == TXL_NONE && st >= RS_ILLNESS) nw = (nw & 0xFFFFu) | day << 16;
+        if (nw != lw) L[i] = nw;
+    }
+}
+
 // four waves a workgroup, one tile a wave and round, the tiles strided over the grid
 template <bool GROUP>
 __global__ __launch_bounds__(TXL_THREADS) void k_txlog_day(const MemberRef *M_, const MemberRef one_, uint32_t *log, size_t stride, uint32_t N, uint32_t day,
@@ -91,20 +109,9 @@ __global__ __launch_bounds__(TXL_THREADS) void k_txlog_day(const MemberRef *M_, 
         }
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-            const uint32_t i = t * TXL_TILE + (uint32_t)j * 64u + lane, st = RH_STATE(w[j]);
-            if (st == RS_SUSCEPTIBLE) continue;
-            if (by_hot) {
-                if (st == RS_INCUBATION && (w[j] >> 24) == d8)
-                    L[i] = TXL_NONE << 16 | day;
-                else if (st == RS_ILLNESS && (w[j] >> 24) == o8)
-                    reinterpret_cast<GAS uint16_t *>(L)[2u * i + 1u] = (uint16_t)day;
-            } else {
-                const uint32_t lw = L[i];
-                uint32_t nw = lw;
-                if ((lw & 0xFFFFu) == TXL_NONE) nw = (nw & 0xFFFF0000u) | day;
-                if ((lw >> 16) == TXL_NONE && st >= RS_ILLNESS) nw = (nw & 0xFFFFu) | day << 16;
-                if (nw != lw) L[i] = nw;
-            }
+            const uint32_t i = t * TXL_TILE + (uint32_t)j * 64u + lane;
+            if (RH_STATE(w[j]) == RS_SUSCEPTIBLE) continue;
+            txl_day_update(L, i, w[j], day, d8, o8, by_hot);
         }
     }
 }
@@ -206,13 +213,18 @@ __global__ __launch_bounds__(TXL_THREADS) void k_txlog_report(const MemberRef *M
 // ---------------------------------------------------------------------------------------------
 // host side
 
+struct reina_course;                         // (k_course.inc: the clinical course log attached to a log)
 struct reina_txlog : attachment {            // (last_day: the last day recorded)
     uint32_t *d_log = nullptr;               // [members][stride]
     size_t stride = 0;                       // words a member: n_agents rounded up to whole tiles
     bool by_hot = true;                      // k_txlog_day's form (REINA_TXLOG_FORM=log: the log word of every active agent; measurement handle)
+    reina_course *course = nullptr;          // attached: the day's launch is k_course_day, which records both
 };
+static int course_launch_day(reina_txlog *l, uint32_t grid, uint32_t day, uint32_t by_hot, hipStream_t s);   // (k_course.inc)
+static void course_detach(reina_course *c);   // (the log goes first: the course refuses from then on)
 
 static void free_txlog(reina_txlog *l) {
+    if (l->course) course_detach(l->course);
     if (l->d_log) (void)hipFree(l->d_log);
     delete l;
 }
@@ -249,7 +261,11 @@ static int txlog_launch_day(reina_txlog *l, uint32_t day, hipStream_t s) {
     const uint32_t by_hot = l->by_hot && l->last_day >= 0 && (int64_t)day == l->last_day + 1 ? 1u : 0u;
     const uint32_t tiles = (N + TXL_TILE - 1u) / TXL_TILE;
     const uint32_t grid = txlog_grid(l, (tiles + TXL_THREADS / 64u - 1u) / (TXL_THREADS / 64u));
-    launch_members(k_txlog_day, l->g, grid, K, TXL_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, N, day, by_hot);
+    if (l->course) {
+        if (int rc = course_launch_day(l, grid, day, by_hot, s)) return rc;
+    } else {
+        launch_members(k_txlog_day, l->g, grid, K, TXL_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, N, day, by_hot);
+    }
     l->last_day = day;
     return REINA_OK;
 }

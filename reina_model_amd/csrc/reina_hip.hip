@@ -1458,6 +1458,9 @@ int reina_profile_read(reina_engine_t *e, double *scan_ms_total, uint64_t *scan_
 // the dated transmission log (include/reina_txlog.h): kernels and entry points
 #include "k_txlog.inc"
 
+// the clinical course log attached to a transmission log (include/reina_course.h): kernels and entry points
+#include "k_course.inc"
+
 // lineage reports: mixing by period and trees by seeding period (include/reina_lineage.h): kernels and entry points
 #include "k_lineage.inc"
 

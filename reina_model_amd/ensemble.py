@@ -25,7 +25,7 @@ from .dayrun import History, replay_plan
 from .filtering import particle_filter  # noqa: F401  (conditioned ensembles: reina_model_amd/filtering.py)
 
 
-def run_group_plan(contexts, plan, record_history=True, member_plans=None, group=None, policy=None, txlog=False, summary=None):
+def run_group_plan(contexts, plan, record_history=True, member_plans=None, group=None, policy=None, txlog=False, summary=None, course=False):
     """Execute `plan` (Context.make_plan) for all `contexts` as one engine group.  Returns
     history[len(contexts), days, COUNTER_WORDS] (host) or None.
 
@@ -45,6 +45,10 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
     long as they do (and keeps a group made for the run open).  A later call with the same `group` continues them; members that keep logs already are continued
     whatever `txlog` says.  Not together with a policy.
 
+    `course`: every member keeps a clinical course log too (reina_model_amd/course.py), attached to the group's transmission
+    log and recorded by the same launch; implies `txlog`.  The members' course logs end up on `contexts[m].course_log`
+    (course_reports(contexts): one launch for all).
+
     `summary` (summary.SummarySpec): an EnsembleSummary (quantile bands, peaks, exceedance: reina_model_amd/summary.py) is
     returned in place of the history, computed where the rows are: a device group's rows are never read back.  The members'
     final counters are checked as always."""
@@ -54,6 +58,7 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
     if summary is not None:
         from . import summary as _summ
         _summ.check_group(summary, contexts, plan, record_history)
+    txlog = txlog or course
     logged = [c.transmission_log is not None for c in contexts]
     if (txlog or any(logged)) and policy is not None:
         raise ValueError('run_group_plan: a transmission log and a policy cannot be combined')
@@ -93,6 +98,13 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
         glog = _txl.DeviceLog(contexts[0].engine, group=group)
         for m, c in enumerate(contexts):
             c.transmission_log = _txl.TransmissionLog(c, device=glog, member=m)
+    if course and glog.course is None:
+        from . import course as _crs
+        if any(c.course_log is not None for c in contexts):
+            raise ValueError("run_group_plan: the members' course logs are not those of this group")
+        gcourse = _crs.DeviceCourse(glog)
+        for m, c in enumerate(contexts):
+            c.course_log = _crs.CourseLog(c, device=gcourse, member=m)
     a = group.alloc
     days, start_day = plan['days'], plan['start_day']
     hist = History(days, record_history, group=group)
@@ -399,3 +411,17 @@ def lineage_reports(contexts, period=7, n_periods=None, age_groups=None):
     if glog is not None and getattr(glog.engine, 'lineage_f', None) is not None:
         return _lin.report_group(glog, contexts, period, n_periods, age_groups)
     return [c.transmission_log.lineage_report(period, n_periods, age_groups) for c in contexts]
+
+
+def course_reports(contexts, age_groups=None, n_days=None):
+    """course.CourseReport of every context, between the same two days.  The members of a coursed group (run_group_plan(...,
+    txlog=True, course=True)) are reported by ONE launch (reina_course_report); contexts that keep course logs of their own one
+    by one."""
+    from . import course as _crs
+    contexts = list(contexts)
+    if any(c.course_log is None for c in contexts):
+        raise ValueError('course_reports: a context keeps no course log')
+    glog = _logged_group(contexts)
+    if glog is not None and glog.course is not None and all(c.course_log.device is glog.course for c in contexts):
+        return _crs.report_group(glog.course, contexts, age_groups, n_days)
+    return [c.course_log.report(age_groups, n_days) for c in contexts]

@@ -228,18 +228,20 @@ class Context:
     """MI355X-native agent engine with the reference `Context` protocol (main.pyx:1746-2101)."""
 
     def __init__(self, population_params, healthcare_params, disease_params, start_date,
-                 random_seed=4321, device='cuda:0', engine_factory=None, comm=None, strict=False, policy=None, txlog=False):
+                 random_seed=4321, device='cuda:0', engine_factory=None, comm=None, strict=False, policy=None, txlog=False, course=False):
         """`comm` (sharding.TorchComm or compatible: .rank, .world, .all_reduce_sum/max) makes this
         Context one shard of a population split over comm.world engine instances; population,
         beds, ICU units and import / vaccination quotas given here are the GLOBAL ones.
         `policy` (policy.Policy): run() and run_plan() take the policy route (reina_model_amd/policy.py).
-        `txlog`: keep a dated transmission log from the start (reina_model_amd/txlog.py; start_transmission_log())."""
+        `txlog`: keep a dated transmission log from the start (reina_model_amd/txlog.py; start_transmission_log()).
+        `course`: keep a clinical course log too (reina_model_amd/course.py; start_course_log()); implies `txlog`."""
         from .sharding import split_count, split_population
         self.comm = comm
         self.strict = bool(strict)   # iterate() raises on the day of a problem (main.pyx:2017-2018)
         self.policy = policy
         self.policy_levels = None    # after a policy run: the level in force on each of its days
         self.transmission_log = None  # txlog.TransmissionLog once begun: run(), run_plan() and iterate() record every day
+        self.course_log = None        # course.CourseLog once begun: recorded with the transmission log it is attached to
         if policy is not None and comm is not None and (comm.world > 1 or getattr(comm, 'always_collective', False)):
             raise ValueError('policy: sharded Contexts are refused (the signal would need the all-reduce of the shards)')
         # testing aid: take the begin / all-reduce / end path even with a single shard
@@ -396,8 +398,23 @@ class Context:
         # main.pyx:1780-1781: the initial condition is applied last, before any intervention exists
         if ipc is not None and ipc.has_initial_state():
             self._set_initial_state(ipc)
-        if txlog:
+        if txlog or course:
             self.start_transmission_log()
+        if course:
+            self.start_course_log()
+
+    def start_course_log(self):
+        """Begin a clinical course log (course.CourseLog, also ctx.course_log): from now on every day that the transmission
+        log records also dates every agent's detection, admission, ICU admission and outcome.  It is attached to the
+        transmission log, which is begun here when the Context keeps none, and lives where that lives; whatever has happened
+        already gets the code BEFORE.  May be called mid-run.  Everything a transmission log refuses is refused."""
+        from . import course as _crs
+        if self.course_log is not None:
+            raise ValueError('start_course_log: this Context keeps a course log already')
+        if self.transmission_log is None:
+            self.start_transmission_log()
+        self.course_log = _crs.CourseLog(self)
+        return self.course_log
 
     def start_transmission_log(self):
         """Begin a dated transmission log (txlog.TransmissionLog, also ctx.transmission_log): from now on run(), run_plan()

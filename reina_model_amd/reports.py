@@ -182,6 +182,13 @@ class Report:
     def _groups(self):
         return self.group_labels or [str(k) for k in range(self.n_groups)]
 
+    def _dates(self):
+        """the index of a table by day (reports with n_days and start_date): dates from start_date, day numbers without one"""
+        import pandas as pd
+        if self.start_date is None:
+            return pd.RangeIndex(self.n_days, name='day')
+        return pd.date_range(str(self.start_date), periods=self.n_days, name='date')
+
     def __eq__(self, other):
         return isinstance(other, type(self)) and all(getattr(self, k) == getattr(other, k) for k in self.IDENTITY) \
             and np.array_equal(self.words, other.words)

@@ -53,14 +53,16 @@ def create_disease_params(variables):
 
 
 def make_context(variables, age_counts=None, seed=None, interventions=None, device='cuda:0',
-                 engine_factory=None, comm=None, ipc=None, strict=False, snapshot=None, policy=None, txlog=False):
+                 engine_factory=None, comm=None, ipc=None, strict=False, snapshot=None, policy=None, txlog=False,
+                 course=False):
     """Build a Context the way calc/simulation.py:148-180 does.  `ipc`: an InitialPopulationCondition,
     a dict of its fields, None (no initial condition), or 'auto' = what simulate_individuals passes,
     datasets.get_initial_population_condition(variables) (calc/simulation.py:152).
     `snapshot` (snapshot.Snapshot): the Context continues from it (Context.restore); no initial condition is applied, the
     state is replaced.  `policy` (policy.Policy): triggered interventions -- run() takes the policy route.
     `txlog`: keep a dated transmission log (Context.start_transmission_log; begun after the restore when a snapshot is given:
-    everything the snapshot holds is BEFORE)."""
+    everything the snapshot holds is BEFORE).  `course`: keep a clinical course log as well (Context.start_course_log); implies
+    `txlog`."""
     if snapshot is not None:
         ipc = None
     if isinstance(ipc, str) and ipc == 'auto':
@@ -80,7 +82,7 @@ def make_context(variables, age_counts=None, seed=None, interventions=None, devi
     ctx = model.Context(pop_params, hc, create_disease_params(variables), variables['start_date'],
                         random_seed=variables['random_seed'] if seed is None else seed,
                         device=device, engine_factory=engine_factory, comm=comm, strict=strict, policy=policy,
-                        txlog=bool(txlog) and snapshot is None)
+                        txlog=bool(txlog) and snapshot is None, course=bool(course) and snapshot is None)
     if interventions is None:
         ivs = get_active_interventions(variables)
     else:
@@ -90,8 +92,10 @@ def make_context(variables, age_counts=None, seed=None, interventions=None, devi
         ctx.add_intervention(iv)
     if snapshot is not None:
         ctx.restore(snapshot)
-        if txlog:
+        if txlog or course:
             ctx.start_transmission_log()
+        if course:
+            ctx.start_course_log()
     return ctx
 
 

@@ -223,12 +223,6 @@ class LogReport(_rep.Report):
     def __repr__(self):
         return 'LogReport(days=%d, infected=%d, dated=%d, before=%d, links=%d)' % (self.n_days, self.infected, self.dated, self.before, self.links)
 
-    def _dates(self):
-        import pandas as pd
-        if self.start_date is None:
-            return pd.RangeIndex(self.n_days, name='day')
-        return pd.date_range(str(self.start_date), periods=self.n_days, name='date')
-
     def _v(self, arr, variant):
         """one variant's part of an array ([variant, ...] or [day, variant, ...]), or the sum over the variants"""
         axis = 0 if arr.ndim == 2 else 1
@@ -297,6 +291,7 @@ class DeviceLog:
         f = _rep.entry_points(engine, 'txlog_f', 'transmission-log', 'reina_txlog.h')
         self.f, self.engine, self.group = f, engine, group
         self.members = 1 if group is None else len(group.engines)
+        self.course = None   # course.DeviceCourse once one is attached: the record launches record it too
         self._h = ctypes.c_void_p()
         if group is None:
             engine._check(f['txlog_create'](engine._h, engine.alloc.stream(), ctypes.byref(self._h)), 'txlog_create')
@@ -304,6 +299,8 @@ class DeviceLog:
             engine._check(f['group_txlog_create'](group._h, engine.alloc.stream(), ctypes.byref(self._h)), 'group_txlog_create')
 
     def close(self):
+        if self.course is not None:
+            self.course.close()
         if self._h:
             self.f['txlog_destroy'](self._h)
             self._h = ctypes.c_void_p()
@@ -360,6 +357,7 @@ class TransmissionLog:
         check_capable(ctx)
         self.ctx, self.member = ctx, int(member)
         self.begin_day = int(ctx.day)
+        self.course = None   # course.CourseLog once one is attached (Context.start_course_log)
         self.device, self._words = device, None
         if device is None:
             if not host and _eng.is_device(ctx.engine) and ctx.engine.txlog_f is not None:
@@ -380,7 +378,10 @@ class TransmissionLog:
         if self.device is not None:
             self.device.record_day(day)
         else:
-            self._words = record_numpy(self._words, _host_array(self.ctx.engine.tensors['hot']), day)
+            hot = _host_array(self.ctx.engine.tensors['hot'])
+            self._words = record_numpy(self._words, hot, day)
+            if self.course is not None:
+                self.course.record_host(hot, day)
 
     def words(self):
         """uint32[n_agents], a host copy"""
@@ -423,7 +424,8 @@ class TransmissionLog:
         agent, age, infector (-1: an import or the initial condition), infector_age (-1 without one), infection_day and
         onset_day (-1 NONE, -2 BEFORE), variant, severity, state, detected, n_infected.  The infector column holds every
         infector word that is in range, that of a bad link (a self-link, a link to a susceptible agent) included: a row has an
-        infector when its word names an agent, not only when reports.links calls it linked."""
+        infector when its word names an agent, not only when reports.links calls it linked.  With a course log attached
+        (course.py): detection_day, admission_day, icu_day and outcome_day as well."""
         import pandas as pd
         hot, infector, n_infected, _ = _rep.host_state(self.ctx.engine)
         log = self.words()
@@ -431,11 +433,15 @@ class TransmissionLog:
         age = _rep.age_lookup(self.ctx.age_start, np.zeros(self.ctx.nr_ages, dtype=np.int64))[3]   # (the ages alone: no groups here)
         has = (src >= 0) & (src < len(hot))
         w = hot[idx]
-        return pd.DataFrame(dict(
+        df = pd.DataFrame(dict(
             agent=idx, age=age(idx), infector=np.where(has, src, -1), infector_age=np.where(has, age(np.where(has, src, 0)), -1),
             infection_day=_signed(log[idx] & 0xFFFF), onset_day=_signed(log[idx] >> 16), variant=((w >> 8) & 3).astype(np.int64),
             severity=np.minimum((w >> 3) & 7, 4).astype(np.int64), state=(w & 7).astype(np.int64), detected=(w & 0x40) != 0,
             n_infected=n_infected.view(np.int32)[idx].astype(np.int64)))
+        if self.course is not None:
+            for name, days in zip(('detection_day', 'admission_day', 'icu_day', 'outcome_day'), self.course.days()):
+                df[name] = days[idx]
+        return df
 
 
 def _signed(half):
@@ -466,6 +472,8 @@ def run_host_driven(ctx, days, record_history=True, on_day=None):
         hot = _host_array(ctx.engine.tensors['hot']).view(np.uint32)
         before = log._words
         log._words = record_numpy(before, hot, d.day)
+        if log.course is not None:
+            log.course.record_host(hot, d.day)
         if on_day is not None:
             on_day(int(d.day), hot, before, log._words)
     ctx._raise_on_problem(ctx.engine.read_counters())

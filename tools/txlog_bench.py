@@ -41,9 +41,11 @@ def worker(root):
 
     def one(leg, agents, days, seed):
         kw = {}
-        if leg.startswith('logged'):
+        if leg.startswith('logged') or leg == 'coursed':
             kw['txlog'] = True
             os.environ['REINA_TXLOG_FORM'] = 'log' if leg == 'logged_log' else 'hot'
+        if leg == 'coursed':   # (tools/course_bench.py: the clinical course log beside the transmission log)
+            kw['course'] = True
         ages = datasets.scaled_population(agents) if agents else None
         ctx = simulation.make_context(v, age_counts=ages, seed=seed, ipc='auto', **kw)
         torch.cuda.synchronize()
@@ -53,6 +55,12 @@ def worker(root):
         out = dict(ms=(time.perf_counter() - t0) * 1e3, n_agents=int(ctx.total_people))
         ci = eng.C_NAMES.index('infected')
         out['infected_by_day'] = [int(x) for x in np.asarray(hist)[:, ci * eng.MAX_AGES:(ci + 1) * eng.MAX_AGES].sum(axis=1)]
+        if leg == 'coursed':
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = ctx.course_log.report()
+            out['report_ms'] = (time.perf_counter() - t0) * 1e3
+            out['report_infected'], out['with_outcome'], out['with_admission'] = r.infected, r.with_outcome, r.with_admission
         if leg == 'logged':
             report_day = min(days, 200 if not agents else 120)
             torch.cuda.synchronize()
@@ -72,15 +80,21 @@ class Worker:
     def __init__(self, root):
         self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), '--worker', '--root', root], stdin=subprocess.PIPE,
                                   stdout=subprocess.PIPE, text=True, cwd=root)
-        assert json.loads(self.p.stdout.readline())['ready']
+        assert self._read('start')['ready']
+
+    def _read(self, what):
+        """the worker's next JSON line (libraries print lines of their own to stdout while they load)"""
+        while True:
+            line = self.p.stdout.readline()
+            if not line:
+                raise RuntimeError('worker died on %s' % what)
+            if line.startswith('{'):
+                return json.loads(line)
 
     def run(self, leg, agents, days, seed=1):
         self.p.stdin.write('%s %d %d %d\n' % (leg, agents, days, seed))
         self.p.stdin.flush()
-        line = self.p.stdout.readline()
-        if not line:
-            raise RuntimeError('worker died on leg %s' % leg)
-        return json.loads(line)
+        return self._read('leg %s' % leg)
 
     def close(self):
         self.p.stdin.close()
