@@ -15,6 +15,7 @@ DEPS = SOURCES + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.e
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_snapshot.h'),
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_transmission.h'),
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_filter.h'),
+                  os.path.join(os.path.dirname(HERE), 'include', 'reina_filter_log.h'),
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_policy.h'),
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_txlog.h'),
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_course.h'),

@@ -88,15 +88,18 @@ __global__ __launch_bounds__(CLONE_THREADS) void k_group_clone(const MemberRef *
     }
 }
 
-extern "C" {
+// what both clones share (reina_group_clone, and reina_group_txlog_clone of k_filter_log.inc): the checks of a pair list and
+// the launches per chunk of REINA_CLONE_MAX_PAIRS pairs.  `what` names the entry point in the messages.  With a log, its
+// launch is queued ahead of the state's in every chunk: it reads the destinations' hot words, which k_group_clone overwrites.
+struct reina_txlog;
+static int txlog_clone_launch(reina_txlog *l, const MemberRef *d_refs, uint32_t tile_blocks, const ClonePairs &a, hipStream_t s);   // (k_filter_log.inc)
 
-int reina_filter_version(void) { return REINA_FILTER_VERSION; }
-
-int reina_group_clone(reina_group_t *g, const uint32_t *pairs, uint32_t n_pairs, void *stream) {
+static int group_clone_pairs(reina_group_t *g, reina_txlog *log, const uint32_t *pairs, uint32_t n_pairs, void *stream, const char *what) {
     if (!g || g->members.empty()) return REINA_E_INVALID;
     if (n_pairs == 0) return REINA_OK;
+    const std::string w(what);
     if (!pairs) {
-        g_last_error = "reina_group_clone: no pair list";
+        g_last_error = w + ": no pair list";
         return REINA_E_INVALID;
     }
     const uint32_t K = (uint32_t)g->members.size();
@@ -105,11 +108,11 @@ int reina_group_clone(reina_group_t *g, const uint32_t *pairs, uint32_t n_pairs,
     for (uint32_t j = 0; j < n_pairs; j++) {
         const uint32_t dst = pairs[2 * j], src = pairs[2 * j + 1];
         if (dst >= K || src >= K) {
-            g_last_error = "reina_group_clone: a member index is out of range";
+            g_last_error = w + ": a member index is out of range";
             return REINA_E_INVALID;
         }
         if (role[dst] & 1u) {
-            g_last_error = "reina_group_clone: a destination appears twice";
+            g_last_error = w + ": a destination appears twice";
             return REINA_E_INVALID;
         }
         role[dst] |= 1u;
@@ -117,7 +120,7 @@ int reina_group_clone(reina_group_t *g, const uint32_t *pairs, uint32_t n_pairs,
     }
     for (uint32_t m = 0; m < K; m++) {
         if (role[m] == 3u) {
-            g_last_error = "reina_group_clone: a source is also a destination";
+            g_last_error = w + ": a source is also a destination";
             return REINA_E_INVALID;
         }
     }
@@ -125,7 +128,7 @@ int reina_group_clone(reina_group_t *g, const uint32_t *pairs, uint32_t n_pairs,
     for (uint32_t j = 0; j < n_pairs; j++) {
         const reina_engine_t *d = g->members[pairs[2 * j]], *s = g->members[pairs[2 * j + 1]];
         if (d->testing_ever != s->testing_ever) {
-            g_last_error = "reina_group_clone: the members' testing_ever flags differ (they ran different plans)";
+            g_last_error = w + ": the members' testing_ever flags differ (they ran different plans)";
             return REINA_E_INVALID;
         }
     }
@@ -142,10 +145,20 @@ int reina_group_clone(reina_group_t *g, const uint32_t *pairs, uint32_t n_pairs,
     for (uint32_t j0 = 0; j0 < n_pairs; j0 += REINA_CLONE_MAX_PAIRS) {
         a.n = n_pairs - j0 < REINA_CLONE_MAX_PAIRS ? n_pairs - j0 : REINA_CLONE_MAX_PAIRS;
         for (uint32_t j = 0; j < a.n; j++) a.p[j] = pairs[2 * (j0 + j)] | pairs[2 * (j0 + j) + 1] << 16;
+        if (log)
+            if (int rc = txlog_clone_launch(log, g->d_refs, tile_blocks, a, s)) return rc;
         hipLaunchKernelGGL(k_group_clone, dim3(tile_blocks + CLONE_DENSE_BLOCKS, a.n), dim3(CLONE_THREADS), 0, s, g->d_refs, a);
         HIP_CHECK(hipGetLastError());
     }
     return REINA_OK;
+}
+
+extern "C" {
+
+int reina_filter_version(void) { return REINA_FILTER_VERSION; }
+
+int reina_group_clone(reina_group_t *g, const uint32_t *pairs, uint32_t n_pairs, void *stream) {
+    return group_clone_pairs(g, nullptr, pairs, n_pairs, stream, "reina_group_clone");
 }
 
 }  // extern "C"

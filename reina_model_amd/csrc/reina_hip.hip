@@ -1461,6 +1461,9 @@ int reina_profile_read(reina_engine_t *e, double *scan_ms_total, uint64_t *scan_
 // the clinical course log attached to a transmission log (include/reina_course.h): kernels and entry points
 #include "k_course.inc"
 
+// the clone of a logged group: the particle filter carries both logs (include/reina_filter_log.h): kernel and entry point
+#include "k_filter_log.inc"
+
 // lineage reports: mixing by period and trees by seeding period (include/reina_lineage.h): kernels and entry points
 #include "k_lineage.inc"
 

@@ -9,7 +9,13 @@ are resampled systematically.  Resampling moves device state only: member dst is
 state (reina_group_clone: one launch for all pairs) and continues as an independent future under its own seed -- the RNG
 is Philox keyed by the seed, so nothing is reseeded, and under one plan the members' host state is the same.
 
-This module also holds clone_state, the numpy specification of the clone and the path for host-memory engines.
+A LOGGED filter (txlog=True / course=True; include/reina_filter_log.h, DESIGN.md section 6d "Logged filters") keeps the dated
+transmission log and the clinical course log of the whole group, and every clone carries them: after it a particle's log is
+the log of its whole ancestral path, so the reports of the final particles (FilterResult.log_reports, course_reports,
+reproduction_number_band, ...) are conditioned on the observations with no stitching on the host.
+
+This module also holds clone_state, the numpy specification of the clone and the path for host-memory engines, and
+clone_log_numpy / clone_course_numpy / clone_log_delta_numpy, those of the logs' clone.
 
 Alignment: an observation dated t is scored against history row d = t - start_date, the state before day d (what the
 reference's frames show on that date).  Rows outside the filter's horizon are ignored.
@@ -26,6 +32,8 @@ from . import engine as _eng
 FILTER_VERSION = 1              # include/reina_filter.h: REINA_FILTER_VERSION
 CLONE_MAX_PAIRS = 896           # REINA_CLONE_MAX_PAIRS: pairs per launch
 FILTER_FUNCTIONS = ('filter_version', 'group_clone')
+FILTER_LOG_VERSION = 1          # include/reina_filter_log.h: REINA_FILTER_LOG_VERSION
+FILTER_LOG_FUNCTIONS = ('filter_log_version', 'group_txlog_clone')
 TILE = 512
 # k_init's cold record: claim (2 words) ~0, infector -1, n_infected 0, onset 0.0, vacc_day -1, first_infectee -1, next_sibling -1
 COLD_DEFAULT = np.array([0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF, 0, 0, 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF], dtype=np.uint32)
@@ -39,6 +47,12 @@ def bind_filter_abi(lib, prefix):
     """The particle-filter entry points of a library, or None when it has none."""
     argtypes = {'group_clone': [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]}
     return _eng.bind_optional_abi(lib, prefix, FILTER_FUNCTIONS, argtypes, 'filter_version', FILTER_VERSION)
+
+
+def bind_filter_log_abi(lib, prefix):
+    """The logged clone's entry points of a library (include/reina_filter_log.h), or None when it has none."""
+    argtypes = {'group_txlog_clone': [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]}
+    return _eng.bind_optional_abi(lib, prefix, FILTER_LOG_FUNCTIONS, argtypes, 'filter_log_version', FILTER_LOG_VERSION)
 
 
 # ------------------------------------------------------------------------------------------------ the clone
@@ -91,18 +105,63 @@ def check_pairs(pairs, K):
     return p
 
 
-def _check_no_logs(contexts):
-    """a clone overwrites a member's state but not its dated transmission log (reina_model_amd/txlog.py)"""
-    if any(getattr(c, 'transmission_log', None) is not None for c in contexts):
-        raise ValueError('particle filter: members that keep a transmission log are refused (a clone overwrites a '
-                         "member's state but not its log)")
+def clone_log_numpy(dst_words, src_words):
+    """The specification of reina_group_txlog_clone for one pair's log words (uint32 [n]): a dense copy, in place."""
+    dst_words[:] = src_words
+    return dst_words
 
 
-def clone_group(group, pairs):
+def clone_course_numpy(dst_records, src_records):
+    """... and for one pair's course records (uint64 [n])"""
+    dst_records[:] = src_records
+    return dst_records
+
+
+def clone_log_delta_numpy(dst, src, dst_hot, src_hot):
+    """k_txlog_clone's rule, for log words and for course records alike, in place: an agent whose hot word is non-zero in
+    either member gets src's word; agents susceptible in both are not touched.  Equal to the dense copy on the logs'
+    invariant: hot == 0 => the log word is NONE | NONE << 16 and the record four NONE (the begin and record passes write only
+    where the state is not 0, and a hot word never returns to 0)."""
+    touched = (np.asarray(dst_hot).view(np.uint32).ravel() != 0) | (np.asarray(src_hot).view(np.uint32).ravel() != 0)
+    dst[touched] = np.asarray(src)[touched]
+    return dst
+
+
+def _group_log(contexts, group):
+    """The txlog.DeviceLog of a filter's members: None when none of them keeps a transmission log, the group's log when
+    they are the whole of ONE logged group and that group is `group` (ensemble._logged_group).  A clone carries the log of
+    its group only: members that keep logs of their own, or of another group, are refused."""
+    logged = [getattr(c, 'transmission_log', None) is not None for c in contexts]
+    if not any(logged):
+        return None
+    if all(logged) and group is not None:
+        from . import ensemble
+        glog = ensemble._logged_group(contexts)
+        if glog is not None and glog.group is group:
+            return glog
+    raise ValueError('particle filter: members that keep a transmission log of their own, or of another group, are refused '
+                     "(a clone carries the log of the filter's own group only: particle_filter(..., txlog=True))")
+
+
+def clone_group(group, pairs, log=None):
     """Member dst of the engine group gets member src's carried state, for every (dst, src) in `pairs`: ONE launch on the
-    device (reina_group_clone), clone_state per pair for host-memory engines."""
+    device (reina_group_clone), clone_state per pair for host-memory engines.  `log` (the txlog.DeviceLog of this group):
+    dst gets src's log words as well, and its course records when a course is attached -- one call
+    (reina_group_txlog_clone: the log's launch ahead of the state's)."""
     engines = group.engines
     e0 = engines[0]
+    if log is not None:
+        from . import reports as _rep
+        f = _rep.entry_points(e0, 'filter_log_f', 'logged-clone', 'reina_filter_log.h')
+        if getattr(log, 'group', None) is not group:
+            raise ValueError('clone: `log` is not the transmission log of this group')
+        flat = [int(x) for pr in pairs for x in pr]
+        if len(flat) % 2:
+            raise ValueError('clone: pairs are (dst, src)')
+        arr = (ctypes.c_uint32 * max(len(flat), 1))(*[x & 0xFFFFFFFF for x in flat])
+        _eng.mark_stale(engines)
+        e0._check(f['group_txlog_clone'](log._h, arr, len(flat) // 2, e0.alloc.stream()), 'group_txlog_clone')
+        return
     if not _eng.is_device(e0):
         p = check_pairs(pairs, len(engines))
         mq = min(e.config.max_queue for e in engines)
@@ -296,12 +355,14 @@ def assign_in_place(counts):
 
 class FilterResult:
     """What particle_filter returns: per window (start_day, days, loglik [K], ess, ancestors [K], resampled); log_evidence;
-    the final weights; the planner and the member Contexts (their engine group stays open for forecast(); close())."""
+    the final weights; the planner and the member Contexts (their engine group stays open for forecast(); close()).
+    Of a logged filter also the posterior over what the logs report: log_reports / lineage_reports / course_reports of the
+    final particles, and the weighted bands of R_c, incidence and admissions by date."""
 
     def __init__(self, planner, contexts, group, start_day, start_date, filter_seed):
         self.planner = planner
         self.contexts = contexts
-        _check_no_logs(contexts)
+        _group_log(contexts, group)
         self.group = group
         self.start_day = start_day
         self.start_date = _as_date(start_date)
@@ -364,25 +425,110 @@ class FilterResult:
         """per-date quantiles of a POP_ATTRS total over the final particles, weighted by the final weights (inverted CDF):
         a DataFrame indexed by date, one column per q"""
         import pandas as pd
-        tot = self.totals(attr).astype(np.float64)
+        q = [float(x) for x in np.atleast_1d(q)]
+        return pd.DataFrame(self.weighted_band(self.totals(attr).astype(np.float64), q), index=self.dates(), columns=q)
+
+    def weighted_band(self, values, q=(0.05, 0.5, 0.95)):
+        """[T, len(q)]: per column of `values` [K, T] (float64, one row per final particle) the quantiles under the final
+        weights, by the inverted CDF -- the smallest value at which the cumulated weight reaches q.  Members whose value is
+        not finite are left out of their column and the weights renormalised; a column with no finite value is NaN."""
+        values = np.asarray(values, dtype=np.float64)
+        if values.ndim != 2 or values.shape[0] != self.n_particles:
+            raise ValueError('weighted_band: values are [n_particles, T]')
         w = self.weights
         q = [float(x) for x in np.atleast_1d(q)]
-        order = np.argsort(tot, axis=0, kind='stable')
-        out = np.zeros((tot.shape[1], len(q)))
-        for d in range(tot.shape[1]):
-            v = tot[order[:, d], d]
-            cw = np.cumsum(w[order[:, d]])
+        out = np.full((values.shape[1], len(q)), np.nan)
+        for d in range(values.shape[1]):
+            keep = np.isfinite(values[:, d])
+            if not keep.any():
+                continue
+            col, wk = values[keep, d], w[keep]
+            order = np.argsort(col, kind='stable')
+            v = col[order]
+            cw = np.cumsum(wk[order])
             for j, x in enumerate(q):
                 out[d, j] = v[min(int(np.searchsorted(cw, x * cw[-1] - 1e-12, side='left')), len(v) - 1)]
-        return pd.DataFrame(out, index=self.dates(), columns=q)
+        return out
+
+    def weighted_mean(self, values):
+        """[T]: per column of `values` [K, T] the mean under the final weights, over the members whose value is finite (NaN
+        when there is none)"""
+        values = np.asarray(values, dtype=np.float64)
+        keep = np.isfinite(values)
+        w = self.weights[:, None] * keep
+        tot = w.sum(axis=0)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.where(tot > 0, (np.where(keep, values, 0.0) * w).sum(axis=0) / tot, np.nan)
+
+    # ---- a logged filter: the posterior over the logs' reports
+
+    @property
+    def log(self):
+        """the group's txlog.DeviceLog of a logged filter, None of an unlogged one"""
+        return _group_log(self.contexts, self.group)
+
+    def _logged(self, what, course=False):
+        if self.group is None:
+            raise ValueError('%s: the filter has been closed' % what)
+        glog = self.log
+        if glog is None:
+            raise ValueError('%s: the filter keeps no transmission log (particle_filter(..., txlog=True))' % what)
+        if course and glog.course is None:
+            raise ValueError('%s: the filter keeps no course log (particle_filter(..., course=True))' % what)
+
+    def log_reports(self, age_groups=None, n_days=None):
+        """txlog.LogReport of every final particle -- of its whole ancestral path -- by one launch (ensemble.log_reports)"""
+        from . import ensemble
+        self._logged('log_reports')
+        return ensemble.log_reports(self.contexts, age_groups, n_days)
+
+    def lineage_reports(self, period=7, n_periods=None, age_groups=None):
+        """lineage.LineageReport of every final particle, one launch per pass (ensemble.lineage_reports)"""
+        from . import ensemble
+        self._logged('lineage_reports')
+        return ensemble.lineage_reports(self.contexts, period, n_periods, age_groups)
+
+    def course_reports(self, age_groups=None, n_days=None):
+        """course.CourseReport of every final particle by one launch (ensemble.course_reports); needs course=True"""
+        from . import ensemble
+        self._logged('course_reports', course=True)
+        return ensemble.course_reports(self.contexts, age_groups, n_days)
+
+    def _band_frame(self, values, q, index, means=()):
+        import pandas as pd
+        q = [float(x) for x in np.atleast_1d(q)]
+        df = pd.DataFrame(self.weighted_band(values, q), index=index, columns=q)
+        for name, v in means:
+            df[name] = self.weighted_mean(v)
+        return df
+
+    def reproduction_number_band(self, q=(0.05, 0.5, 0.95), variant=None):
+        """By date of infection: the weighted quantiles over the final particles of the case reproduction number R_c
+        (LogReport.case_reproduction_number; a particle whose cohort of the date is empty is left out of that date), one
+        column per q, and the weighted means of the cohort's size (`cohort`) and of its closed share (`closed_share`: R_c of an
+        open cohort is censored)."""
+        frames = [r.case_reproduction_number(variant) for r in self.log_reports()]
+        col = lambda name: np.stack([f[name].to_numpy(dtype=np.float64) for f in frames])
+        return self._band_frame(col('r_c'), q, frames[0].index, (('cohort', col('cohort')), ('closed_share', col('closed_share'))))
+
+    def incidence_band(self, q=(0.05, 0.5, 0.95)):
+        """infections by date of infection, summed over variants and age groups: the weighted quantiles over the final particles"""
+        reps = self.log_reports()
+        return self._band_frame(np.stack([r.incidence.sum(axis=(1, 2), dtype=np.uint64).astype(np.float64) for r in reps]), q, reps[0]._dates())
+
+    def admissions_band(self, q=(0.05, 0.5, 0.95)):
+        """admissions by date, summed over age groups: the weighted quantiles over the final particles; needs course=True"""
+        reps = self.course_reports()
+        return self._band_frame(np.stack([r.admissions.sum(axis=1, dtype=np.uint64).astype(np.float64) for r in reps]), q, reps[0]._dates())
 
     def forecast(self, days):
         """continue the group `days` days with the planner's next plan, no observations (weights unchanged); returns
-        history [K, days, COUNTER_WORDS]; paths() and quantiles() then extend over them"""
+        history [K, days, COUNTER_WORDS]; paths() and quantiles() then extend over them.  A logged filter's logs are
+        continued (its reports then reach the forecast's last day)"""
         from . import ensemble
         if self.group is None:
             raise ValueError('forecast: the filter has been closed')
-        _check_no_logs(self.contexts)
+        _group_log(self.contexts, self.group)
         d0 = self.start_day + self.days
         plan = self.planner.make_plan(int(days))
         hist = ensemble.run_group_plan(self.contexts, plan, group=self.group)
@@ -392,21 +538,33 @@ class FilterResult:
         return hist
 
     def close(self):
+        """closes the engine group, and a logged filter's log (and course) with it"""
         if self.group is not None:
+            try:
+                glog = _group_log(self.contexts, self.group)
+            except ValueError:
+                glog = None
+            if glog is not None:
+                for c in self.contexts:
+                    c.transmission_log = c.course_log = None
+                glog.close()
             self.group.close()
             self.group = None
 
 
 def particle_filter(variables, n_particles, observations=None, obs_model=None, window=7, days=None, seeds=None,
                     filter_seed=0, ess_threshold=0.5, device='cuda:0', engine_factory=None, age_counts=None, snapshot=None,
-                    comm=None):
+                    comm=None, txlog=False, course=False):
     """Bootstrap particle filter of `n_particles` members of the scenario `variables` (seeds[m], default 0 .. K - 1) on
     `observations` (a DataFrame indexed by date, e.g. datasets.get_detected_cases; None: no observations, which is
     run_group_plan of the same seeds).  Windows of `window` days; after each one the members are scored with obs_model
     (default ObservationModel()) and resampled systematically (one uniform of numpy's PCG64(filter_seed) per resample) when
     the ESS < ess_threshold * K.  `days` (default: up to the last observed date, else variables['simulation_days']).
-    `snapshot`: every member starts from that realised past (one group unpack, as ensemble.run_branches).  Returns a
-    FilterResult.  Sharded Contexts, K < 2, unknown streams and observations with no date inside the horizon are refused
+    `snapshot`: every member starts from that realised past (one group unpack, as ensemble.run_branches).
+    `txlog`: the group keeps a dated transmission log (txlog.py), begun with the first window (with `snapshot`, the past is
+    BEFORE), and every clone carries it (reina_group_txlog_clone); `course`: a clinical course log too (course.py; implies
+    txlog).  The logs observe and never steer: histories, ancestors and evidence are those of the unlogged filter.  An engine
+    library without the entry points raises EngineError.  Returns a FilterResult.  Sharded Contexts, K < 2, unknown streams and observations with no date inside the horizon are refused
     (ValueError; `comm`, a sharded population's communicator, is accepted only to be refused the same way); a failing
     member raises SimulationFailed."""
     from . import ensemble, simulation
@@ -435,6 +593,10 @@ def particle_filter(variables, n_particles, observations=None, obs_model=None, w
     planner = mk(seeds[0])
     if planner.n_shards != 1 or planner.always_collective:
         raise ValueError('particle_filter: sharded Contexts are not filtered')
+    txlog = bool(txlog or course)
+    if txlog:
+        from . import reports as _rep
+        _rep.entry_points(planner.engine, 'filter_log_f', 'logged-clone', 'reina_filter_log.h')
     if snapshot is not None:
         planner.restore(snapshot, engine_state=False)
     start_day = int(planner.day)
@@ -471,7 +633,8 @@ def particle_filter(variables, n_particles, observations=None, obs_model=None, w
             n = min(window, start_day + days - day)
             t0 = time.perf_counter()
             plan = planner.make_plan(n)
-            hist = ensemble.run_group_plan(ctxs, plan, group=group)
+            hist = ensemble.run_group_plan(ctxs, plan, group=group, txlog=txlog, course=course) if txlog else \
+                ensemble.run_group_plan(ctxs, plan, group=group)
             t1 = time.perf_counter()
             ll = scorer.score(hist, day) if scorer is not None else np.zeros(K)
             t2 = time.perf_counter()
@@ -488,7 +651,10 @@ def particle_filter(variables, n_particles, observations=None, obs_model=None, w
                     scorer.permute(anc)
             t3 = time.perf_counter()
             if pairs:
-                clone_group(group, pairs)
+                if txlog:
+                    clone_group(group, pairs, log=ctxs[0].transmission_log.device)
+                else:
+                    clone_group(group, pairs)
             t4 = time.perf_counter()
             res.windows.append(dict(start_day=day, days=n, loglik=ll, ess=e, ancestors=anc, resampled=resampled,
                                     history=hist, observed=scorer is not None))

@@ -10,10 +10,20 @@ Cases:
              synchronised.
   clone_1e7  K = 16 members of 10^7 agents run 120 days as a group; members 8..15 get the states of members 0..7: the clone
              against the snapshot route on that pair list.
+  --logged   (alone; writes profiles/filter_log_bench.json) the HUS case three ways -- unlogged, with the transmission log
+             (txlog=True), with log and course (course=True): the filter's wall time per window (synchronised at the end), and,
+             after 7 more days, the synchronised clone of the last resample's pair list (reina_group_clone, or
+             reina_group_txlog_clone: the log's launch ahead of the state's), median of --reps.  Every leg runs in a process of
+             its own, the legs alternating over --rounds rounds (medians, min and max over the rounds); --parent DIR, a built
+             checkout of the parent commit, runs the unlogged leg there as well.  --windows W caps the filter at W windows.
+             `wall_ms_per_window`: what the windows took (run, score, resample, clone issue; the members' construction is not
+             in it) over their number.  Bytes the log's launch adds, from the shapes: 8 B per agent and pair (both hot words),
+             and per agent recorded in either member 4 B read + 4 B written of log, 12 + 12 with a course (a dense copy: 8 or
+             24 B per agent).
 Bytes of a clone, from the shapes and the recorded-agent counts: per pair 8 B per agent (both hot words), 64 B read + 64 B
 written per agent the source has recorded, 64 B written per agent only the destination has, 4 B per changed hot word, the
 bit-plane words (16 B per tile read and written), the dense blocks and the source's queues; over 6.3 TB/s.
-usage: python tools/filter_bench.py [--quick] [--out PATH]"""
+usage: python tools/filter_bench.py [--quick] [--logged [--parent DIR] [--windows W] [--rounds N]] [--out PATH]"""
 import argparse
 import copy
 import json
@@ -24,7 +34,8 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+# (a worker of --logged imports the package of the tree it is told: --root DIR)
+sys.path.insert(0, os.path.abspath(sys.argv[sys.argv.index('--root') + 1]) if '--root' in sys.argv[:-1] else ROOT)
 
 from reina_model_amd import datasets, engine as eng, ensemble, filtering, simulation, snapshot as snapmod  # noqa: E402
 from reina_model_amd.variables import VARIABLE_DEFAULTS  # noqa: E402
@@ -151,6 +162,115 @@ def case_hus(K, windows_cap, reps):
         r.close()
 
 
+def log_clone_bytes(contexts, pairs, course):
+    """bytes k_txlog_clone moves for `pairs` beyond the state's clone: (delta, dense)"""
+    n = contexts[0].engine.config.n_agents
+    hot = {m: contexts[m].engine.tensors['hot'].cpu().numpy().view(np.uint32) for pr in pairs for m in pr}
+    either = sum(int(np.count_nonzero((hot[d] != 0) | (hot[s] != 0))) for d, s in pairs)
+    per = 24 if course else 8
+    return 8 * n * len(pairs) + per * either, per * n * len(pairs), either
+
+
+def timed_clone(contexts, group, pairs, reps, log):
+    """the synchronised clone of `pairs`, ms per rep; before every rep the destinations get their own states back (not timed),
+    so each rep moves what a real resample moves (the log's launch moves the same bytes whatever the words hold)"""
+    disease = contexts[0]._disease
+    own = {d: snapmod.pack_engine(contexts[d].engine, disease, testing_ever=True) for d, _ in pairs}
+    ts = []
+    for _ in range(reps + 1):
+        for d, img in own.items():
+            snapmod.unpack_engine(contexts[d].engine, disease, img)
+        sync()
+        t0 = time.perf_counter()
+        if log is None:
+            filtering.clone_group(group, pairs)
+        else:
+            filtering.clone_group(group, pairs, log=log)
+        sync()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return ts[1:]
+
+
+LEGS = {'unlogged': {}, 'txlog': dict(txlog=True), 'course': dict(course=True)}
+
+
+def one_leg(leg, K, windows_cap, reps):
+    """one leg of --logged in this process: the HUS filter (wall time, synchronised at the end), 7 more days, the timed clone"""
+    kw = LEGS[leg]
+    v = copy.deepcopy(VARIABLE_DEFAULTS)
+    obs = datasets.get_detected_cases('HUS')
+    model = filtering.ObservationModel({'all_detected': 10.0, 'in_ward': 10.0})
+    days = None if windows_cap is None else 7 * windows_cap
+    sync()
+    t0 = time.perf_counter()
+    r = filtering.particle_filter(v, K, observations=obs, obs_model=model, window=7, days=days, seeds=list(range(1, K + 1)),
+                                  filter_seed=0, **kw)
+    sync()
+    wall = time.perf_counter() - t0
+    try:
+        run_ms = [t['run'] * 1e3 for t, w in zip(r.timings, r.windows) if w['days'] == 7]
+        pairs = None
+        for w in reversed(r.windows):
+            if w['resampled']:
+                anc = w['ancestors']
+                pairs = [(int(d), int(anc[d])) for d in range(K) if anc[d] != d]
+                break
+        res = dict(leg=leg, agents=r.contexts[0].engine.config.n_agents, days=r.days, windows=len(r.windows),
+                   resamples=int(sum(w['resampled'] for w in r.windows)), log_evidence=r.log_evidence, wall_s=wall,
+                   wall_ms_per_window=sum(sum(t[k] for k in ('run', 'score', 'resample', 'clone')) for t in r.timings) * 1e3 / len(r.windows),
+                   median_window_run_ms=float(np.median(run_ms)))
+        if pairs:
+            r.forecast(7)   # (the destinations differ from their sources again, as they do at a resample)
+            ts = timed_clone(r.contexts, r.group, pairs, reps, r.log if kw else None)
+            res.update(pairs=len(pairs), clone_ms=float(np.median(ts)), clone_ms_all=ts)
+            if kw:
+                delta, dense, either = log_clone_bytes(r.contexts, pairs, 'course' in kw)
+                res.update(log_bytes_delta=delta, log_bytes_dense=dense, recorded_in_either=either,
+                           log_model_ms_at_6p3=delta / PEAK * 1e3)
+        return res
+    finally:
+        r.close()
+
+
+def spread(xs):
+    xs = [float(x) for x in xs]
+    return dict(median=float(np.median(xs)), min=min(xs), max=max(xs), all=xs)
+
+
+def case_logged(K, windows_cap, reps, parent, rounds, on_round=None):
+    """every leg in a process of its own that imports the package of its tree (--leg, --root), the legs alternating round by
+    round; `parent` (a built checkout of the parent commit) runs the unlogged leg as `parent_unlogged`"""
+    import subprocess
+    legs = [('unlogged', ROOT), ('txlog', ROOT), ('course', ROOT)]
+    if parent:
+        legs = [('parent_unlogged', os.path.abspath(parent))] + legs
+    runs = {name: [] for name, _ in legs}
+
+    def summary(rounds_done):
+        out = dict(case='hus_k%d_logged' % K, K=K, rounds=rounds_done, legs={})
+        for name, rs in runs.items():
+            last = {k: x for k, x in rs[-1].items() if k not in ('clone_ms_all', 'leg')}
+            last.update(clone_ms=spread([r['clone_ms'] for r in rs]) if all('clone_ms' in r for r in rs) else None,
+                        wall_ms_per_window=spread([r['wall_ms_per_window'] for r in rs]),
+                        median_window_run_ms=spread([r['median_window_run_ms'] for r in rs]), wall_s=spread([r['wall_s'] for r in rs]),
+                        clone_ms_last_round=rs[-1].get('clone_ms_all'))
+            out['legs'][name] = last
+        out['log_evidence_equal_in_every_leg'] = len({r['log_evidence'] for rs in runs.values() for r in rs}) == 1
+        return out
+
+    for rnd in range(rounds):
+        for name, root in legs:
+            cmd = [sys.executable, os.path.abspath(__file__), '--leg', name.replace('parent_', ''), '--root', root, '--reps', str(reps)]
+            if windows_cap is not None:
+                cmd += ['--windows', str(windows_cap)]
+            out = subprocess.run(cmd, cwd=root, stdout=subprocess.PIPE, text=True, check=True).stdout
+            runs[name].append(json.loads([ln for ln in out.splitlines() if ln.startswith('{"leg"')][-1]))
+            print(json.dumps({name: {k: x for k, x in runs[name][-1].items() if k != 'clone_ms_all'}}), flush=True)
+        if on_round is not None:
+            on_round(summary(rnd + 1))   # (what has been measured so far is kept)
+    return summary(rounds)
+
+
 def case_1e7(n, K, days, reps):
     v = copy.deepcopy(VARIABLE_DEFAULTS)
     ages = datasets.scaled_population(n)
@@ -175,7 +295,25 @@ def main():
     ap.add_argument('--quick', action='store_true', help='4 HUS windows, 10^7 agents at day 60 (for the rocprofv3 run)')
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'filter_bench.json'))
+    ap.add_argument('--logged', action='store_true', help='the logged legs alone (profiles/filter_log_bench.json)')
+    ap.add_argument('--windows', type=int, default=None, help="--logged: so many 7-day windows (default: the case file's span)")
+    ap.add_argument('--parent', default=None, help='--logged: a built checkout of the parent commit, for its unlogged leg')
+    ap.add_argument('--rounds', type=int, default=3, help='--logged: rounds of the alternating legs')
+    ap.add_argument('--leg', default=None, help='(a worker of --logged: this leg, in this process)')
+    ap.add_argument('--root', default=ROOT, help='(a worker of --logged: the tree whose package it imports)')
     a = ap.parse_args()
+    if a.leg:
+        print(json.dumps(one_leg(a.leg, 128, a.windows, a.reps)), flush=True)
+        return
+    if a.logged:
+        out = a.out if a.out != ap.get_default('out') else os.path.join(ROOT, 'profiles', 'filter_log_bench.json')
+
+        def write(case):
+            with open(out, 'w') as f:
+                json.dump(dict(tool='tools/filter_bench.py --logged', peak_bytes_per_s=PEAK, cases=[case]), f, indent=1)
+
+        write(case_logged(128, a.windows, a.reps, a.parent, a.rounds, on_round=write))
+        return
     import torch
     res = dict(device=torch.cuda.get_device_name(0), peak_bytes_per_s=PEAK, cases=[])
     res['cases'].append(case_hus(128, 4 if a.quick else None, a.reps))
