@@ -10,7 +10,9 @@
  * counter block BEFORE day d's opening: the values history row d holds.  kind REINA_POLICY_LEVEL: x(d) = x_now(d);
  * REINA_POLICY_INCREMENT over n = n_days days (1..28): x(d) = x_now(d) - x_now(max(d - n, first)), `first` = the first day of
  * the unbroken sequence of days this policy has seen (a policy keeps the last 32 daily values in a ring; a day that does not
- * follow the last one seen starts a new sequence).  int32 arithmetic, integer comparisons.
+ * follow the last one seen starts a new sequence).  int32 arithmetic, integer comparisons.  The tests hold this on rows whose
+ * absolute values sum to less than 2^31, where every summation order in int32 gives the same x_now; beyond that domain it is
+ * not tested.
  *
  * RULE.  A run starts at level 0.  Day d is a review day when d >= start_day and (d - start_day) % review_every == 0.  On a
  * review day, with l the current level: the run escalates to the highest j > l with x >= up[j - 1], if there is one (jumps

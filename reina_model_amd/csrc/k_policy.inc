@@ -229,6 +229,15 @@ static int policy_begin_run(reina_policy *p) {
     p->e0->policy_lds_crows = crows;
     return REINA_OK;
 }
+// before a run: every day has its trace words (refused as a whole, before any of its days is queued)
+static int policy_check_days(const reina_day_t *days, uint32_t n_days) {
+    for (uint32_t k = 0; k < n_days; k++)
+        if (days[k].day >= REINA_MAX_DAYS) {
+            g_last_error = "policy: day >= REINA_MAX_DAYS (4096): the trace has no words for it";
+            return REINA_E_INVALID;
+        }
+    return REINA_OK;
+}
 static void policy_end_run(reina_policy *p) { p->e0->policy_lds_rows = p->e0->policy_lds_crows = 0; }
 
 int reina_policy_version(void) { return REINA_POLICY_VERSION; }
@@ -267,6 +276,7 @@ int reina_policy_upload_level(reina_policy_t *p, uint32_t level, const reina_con
 int reina_policy_run_days(reina_policy_t *p, const reina_day_t *days, uint32_t n_days, int32_t *history_base, void *stream) {
     if (!days) return REINA_E_INVALID;
     if (int rc = attachment_kind(p, false, "policy: reina_policy_run_days")) return rc;
+    if (int rc = policy_check_days(days, n_days)) return rc;
     if (int rc = policy_begin_run(p)) return rc;
     const int rc = engine_run_days(p->e0, days, n_days, history_base, stream, day_hooks{p, policy_launch_day, nullptr});
     policy_end_run(p);
@@ -276,6 +286,7 @@ int reina_policy_run_days(reina_policy_t *p, const reina_day_t *days, uint32_t n
 int reina_group_policy_run_days(reina_policy_t *p, const reina_day_t *days, uint32_t n_days, int32_t *const *history_bases, void *stream) {
     if (!days) return REINA_E_INVALID;
     if (int rc = attachment_kind(p, true, "policy: reina_group_policy_run_days")) return rc;
+    if (int rc = policy_check_days(days, n_days)) return rc;
     if (int rc = policy_begin_run(p)) return rc;
     const int rc = group_run_days(p->g, days, n_days, history_bases, stream, day_hooks{p, policy_launch_day, nullptr});
     policy_end_run(p);
@@ -283,7 +294,11 @@ int reina_group_policy_run_days(reina_policy_t *p, const reina_day_t *days, uint
 }
 
 int reina_policy_read_trace(reina_policy_t *p, uint32_t first_day, uint32_t n_days, int32_t *out_host, void *stream) {
-    if (!p || (n_days && !out_host)) return REINA_E_INVALID;
+    if (!p) return REINA_E_INVALID;
+    if (n_days && !out_host) {
+        g_last_error = "policy: read_trace without an output buffer (out_host is null)";
+        return REINA_E_INVALID;
+    }
     if ((uint64_t)first_day + n_days > REINA_MAX_DAYS) {
         g_last_error = "policy: trace range beyond REINA_MAX_DAYS";
         return REINA_E_INVALID;

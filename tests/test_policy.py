@@ -1,6 +1,7 @@
 """Triggered interventions (reina_model_amd/policy.py) on the CPU: the rule against hand-written sequences, the plain
 formulation (run_host_driven) on oracle B against dated runs, the level tables against the dated uploads, and the conditions
 the GPU tests' inputs must meet (tests/policy_util.py holds them)."""
+import collections
 import copy
 
 import numpy as np
@@ -290,3 +291,139 @@ def test_frames_carry_the_levels():
     # the mobility column follows the level a day later (the state BEFORE a day)
     assert df['mobility_limitation'].iloc[k + 1] == pytest.approx(0.4)
     assert df['mobility_limitation'].iloc[k] == plain['mobility_limitation'].iloc[k]
+
+
+# ---------------------------------------------------------------------------------------------- 7. the rule on driven signals
+
+def _step_trace(case, m):
+    """step_numpy over member m's days seen, fed the counter blocks the rows are written into: [(level, x)]"""
+    st = case.policy.new_state(pu.START_DATE)
+    lo, hi = pu.signal_range(case.policy)
+    out = []
+    for (a, n, seen), row in zip(case.calls, case.rows[m]):
+        if not seen:
+            continue
+        c = np.zeros(eng.COUNTER_WORDS, dtype=np.int32)
+        c[lo:hi] = row
+        c[lo - 1] = c[hi % eng.COUNTER_WORDS] = 12345      # (the neighbouring rows are not the signal)
+        for d in range(a, a + n):
+            level = pol.step_numpy(st, c, d)
+            out.append((level, st['x']))
+    return out
+
+
+@pytest.mark.parametrize('case', pu.RULE_CASES + [pu.SWITCH_CASE], ids=lambda c: c.name)
+def test_walker_equals_step_numpy(case):
+    for m in range(case.members):
+        want, _ = case.walked[m]
+        got = _step_trace(case, m)
+        bad = [k for k in range(len(want)) if got[k] != want[k]]
+        assert not bad, 'member %d, day %d: step_numpy %s, walker %s' % (m, case.days[bad[0]], got[bad[0]], want[bad[0]])
+
+
+def _changes(case, m):
+    """{day seen: the level in force differs from the one of the last day seen}"""
+    lv = case.levels(m)
+    return dict(zip(case.days, lv != np.concatenate([[0], lv[:-1]])))
+
+
+def test_rule_cases_cover_what_the_issue_lists():
+    rules = [c.rule for c in pu.RULE_CASES]
+    assert len(rules) >= 8 and all(c.members == 6 and 95 <= len(c.days) <= 110 for c in pu.RULE_CASES)
+    assert {len(r.up) + 1 for r in rules} == {2, 3, 5, 8} and {r.kind for r in rules} == {'level', 'increment'}
+    assert {r.n_days for r in rules if r.kind == 'increment'} == {1, 7, 27, 28}
+    assert {r.review_every for r in rules} == {1, 3, 7} and {r.min_days for r in rules} == {0, 2, 9}
+    assert {r.start_day for r in rules} == {0, 4, 11}
+    assert any(min(r.up) < 0 and min(r.down) < 0 for r in rules)
+    assert any(r.up[j] == r.up[j + 1] for r in rules for j in range(len(r.up) - 1))
+    assert any(r.down[j] == r.up[j] for r in rules for j in range(len(r.up)))
+    firsts, gaps = set(), set()
+    for c in pu.RULE_CASES:
+        unseen = [n for _, n, seen in c.calls if not seen]
+        firsts.add(c.days[0])
+        gaps.update(unseen[1:] if c.days[0] else unseen)
+        assert len(unseen) == 2 + (c.days[0] > 0) and all(1 <= n <= 5 for _, n, seen in c.calls if seen)
+        # one member never crosses up[0]
+        assert not c.levels(c.members - 1).any()
+        # a row is 128 words of mixed sign, the ages at and above nr_ages among them, safe under any summation order
+        for m in range(c.members):
+            rows = np.array([r for r in c.rows[m] if r is not None], dtype=np.int64)
+            assert (np.abs(rows).sum(axis=1) < 2 ** 31).all() and (rows < 0).any(axis=1).all() and (rows > 0).any(axis=1).all()
+            assert (rows[:, 101:] != 0).any(axis=1).all()
+            assert list(rows.sum(axis=1)) == [v for v in c.call_value[m] if v is not None]
+    assert firsts == {0, 3, 30} and gaps == {1, 5, 40}
+
+
+def test_rule_cases_take_every_branch():
+    took = sum((c.walked[m][1] for c in pu.RULE_CASES for m in range(c.members)), start=collections.Counter())
+    for b in pu.BRANCHES:
+        assert took[b] >= 10, (b, took[b])
+    assert took['window_at_first'] >= 1
+    mid_call, first_day_change, quiet_call = 0, 0, 0
+    for c in pu.RULE_CASES:
+        eight = len(c.rule.up) == 7
+        if eight:
+            assert {int(x) for m in range(c.members) for x in c.levels(m)} == set(range(8)), c.name
+        for m in range(c.members):
+            ch = _changes(c, m)
+            for a, n, seen in c.calls:
+                if seen:
+                    mid_call += sum(ch[d] for d in range(a + 1, a + n))
+                    first_day_change += bool(ch[a])
+                    quiet_call += not any(ch[d] for d in range(a, a + n))
+        # the ring of an increment: a sequence that wraps it more than once, and one no longer than 20 days
+        runs = np.split(np.array(c.days), np.flatnonzero(np.diff(c.days) != 1) + 1)
+        assert c.rule.kind == 'level' or (max(len(r) for r in runs) > 2 * pol.RING and min(len(r) for r in runs) <= 20)
+    assert mid_call >= 5 and first_day_change >= 1 and quiet_call >= 1
+
+
+def test_switch_case_switches_where_the_issue_says():
+    c = pu.SWITCH_CASE
+    assert 150 <= c.total <= 200 and len(c.days) == c.total and c.rule.kind == 'level' and c.rule.review_every == 1
+    assert c.policy.signal.counter == 'vaccinated' and c.policy.n_levels == 8 and c.rule.min_days == 0
+    assert c.policy.levels[3] == c.policy.levels[4]
+    assert not any(iv[0] == 'vaccinate' for iv in pu.mini_scenario()[0]['interventions'])
+    lv = [int(x) for x in c.levels(0)]
+    pairs = set(zip([0] + lv[:-1], lv))
+    assert {(0, j) for j in range(1, 8)} <= pairs
+    assert any(lv[k:k + 8] == [7, 6, 5, 4, 3, 2, 1, 0] for k in range(len(lv)))
+    assert any(lv[k] < lv[k + 1] < lv[k + 2] for k in range(len(lv) - 2))       # escalations on consecutive days
+    d = pu.SWITCH_DATED_DAY
+    assert lv[d - 1] != lv[d] != lv[d + 1]
+    # the levels' tables: an age window holds more distinct contact rows than the dated tables, a place-only limit and masks
+    # alone hold as many; the two equal levels have the same bytes, every other neighbour differs
+    ctx = pu.make_driven(c, 0, factory=par_engine_factory)
+    bank, _ = pol.build_bank(ctx, c.policy)
+    rows = [len(np.unique(np.concatenate([np.asarray(t[2])[:ctx.nr_ages], np.asarray(t[0])[:ctx.nr_ages, None].view(np.uint32)], axis=1), axis=0))
+            for t in bank]
+    assert rows[1] > rows[0] and rows[6] > rows[0] and rows[2] == rows[3] == rows[5] == rows[0], rows
+    image = [b''.join(np.asarray(x).tobytes() for x in t[:5]) for t in bank]
+    assert [image[k] == image[k + 1] for k in range(7)] == [False, False, False, True, False, False, False]
+    # the members of the group run stand at different levels most days
+    levels = np.stack([c.levels(m) for m in range(c.members)])
+    assert (np.array([len(set(col)) for col in levels.T]) >= 3).mean() > .5
+
+
+@pytest.mark.parametrize('case', pu.RULE_CASES, ids=lambda c: c.name)
+def test_host_driver_on_an_idle_population(case):
+    """the condition the GPU tests rest on: an idle population keeps a written row, and run_host_driven, fed the rows call by
+    call, decides what the walker decides"""
+    for m in range(case.members):
+        ctx = pu.make_driven(case, m, factory=par_engine_factory)
+        hist = pu.run_driven_context(ctx, case, m)
+        lo, hi = pu.signal_range(case.policy)
+        assert np.array_equal(hist[:, lo:hi], case.written(m)), 'member %d: the signal row did not stay as written' % m
+        assert np.array_equal(ctx.policy_levels, case.levels(m)), 'member %d' % m
+
+
+def test_host_driver_on_the_live_epidemic():
+    case = pu.SWITCH_CASE
+    ctx = pu.make_driven(case, 0, factory=par_engine_factory)
+    hist = pu.run_driven_context(ctx, case, 0)
+    lo, hi = pu.signal_range(case.policy)
+    assert np.array_equal(hist[:, lo:hi], case.written(0)), 'the live run touched the vaccinated row'
+    assert np.array_equal(ctx.policy_levels, case.levels(0))
+    plain = pu.make_driven(case, 0, factory=par_engine_factory).run(case.total)
+    ai = eng.C_NAMES.index('all_infected') * eng.MAX_AGES
+    assert plain[-1, ai:ai + eng.MAX_AGES].sum() != hist[-1, ai:ai + eng.MAX_AGES].sum()
+    assert np.array_equal(plain[:6], np.concatenate([hist[:6, :lo], plain[:6, lo:hi], hist[:6, hi:]], axis=1))   # (level 0 until day 6)
