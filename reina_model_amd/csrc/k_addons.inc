@@ -81,19 +81,14 @@ struct AgeGroupArgs {
 };
 
 static int age_group_args(const reina_engine_t *e, const uint8_t *age_group, uint32_t n_groups, uint32_t max_groups, const char *what, AgeGroupArgs *a) {
-    if (!age_group || n_groups < 1u || n_groups > max_groups) {
-        g_last_error = std::string(what) + ": age_group must be a table of groups, 1 <= n_groups <= " + std::to_string(max_groups);
-        return REINA_E_INVALID;
-    }
+    if (!age_group || n_groups < 1u || n_groups > max_groups)
+        return refuse(std::string(what) + ": age_group must be a table of groups, 1 <= n_groups <= " + std::to_string(max_groups));
     std::memset(a, 0, sizeof(*a));
     a->n_agents = e->cfg.n_agents;
     a->nr_ages = e->cfg.nr_ages;
     std::memcpy(a->age_start, e->cfg.age_start, sizeof(a->age_start));
     for (uint32_t k = 0; k < e->cfg.nr_ages; k++) {
-        if (age_group[k] >= n_groups) {
-            g_last_error = std::string(what) + ": an age's group is not below n_groups";
-            return REINA_E_INVALID;
-        }
+        if (age_group[k] >= n_groups) return refuse(std::string(what) + ": an age's group is not below n_groups");
         a->group[k] = age_group[k];
     }
     return REINA_OK;
@@ -200,18 +195,15 @@ struct attachment {
 // an attachment keeps something by day: its launches refuse the days beyond
 static int attachment_check_day(uint32_t day) {
     if (day < REINA_MAX_DAYS) return REINA_OK;
-    g_last_error = "day >= REINA_MAX_DAYS (4096)";
-    return REINA_E_INVALID;
+    return refuse("day >= REINA_MAX_DAYS (4096)");
 }
 
 // attachments hold to bound, unsharded engines: `what` names the attachment, `why_unsharded` is its own reason
 static int attachment_check_members(const std::vector<reina_engine_t *> &members, const char *what, const char *why_unsharded) {
     for (auto m : members) {
         if (!m->bound) return REINA_E_NOT_BOUND;
-        if (m->cfg.n_shards > 1 || m->exact || m->coll_fn || m->a2a_fn) {
-            g_last_error = std::string(what) + ": sharded engines are refused (" + why_unsharded + "), exact attribution included";
-            return REINA_E_INVALID;
-        }
+        if (m->cfg.n_shards > 1 || m->exact || m->coll_fn || m->a2a_fn)
+            return refuse(std::string(what) + ": sharded engines are refused (" + why_unsharded + "), exact attribution included");
     }
     return REINA_OK;
 }
@@ -219,10 +211,8 @@ static int attachment_check_members(const std::vector<reina_engine_t *> &members
 // an entry point of one engine's attachments was handed a group's, or the other way round
 static int attachment_kind(const attachment *a, bool group, const char *what) {
     if (!a) return REINA_E_INVALID;
-    if ((a->g != nullptr) != group) {
-        g_last_error = std::string(what) + (group ? ": made for one engine -- use the entry point without group_" : ": made for a group -- use the reina_group_ entry point");
-        return REINA_E_INVALID;
-    }
+    if ((a->g != nullptr) != group)
+        return refuse(std::string(what) + (group ? ": made for one engine -- use the entry point without group_" : ": made for a group -- use the reina_group_ entry point"));
     return REINA_OK;
 }
 
@@ -240,4 +230,122 @@ static int engine_run_days(reina_engine_t *e0, const reina_day_t *days, uint32_t
             if (int rc = hooks.after(hooks.a, d, (hipStream_t)stream)) return rc;
     }
     return REINA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// what the entry points of the attachments share on the host.  A new attachment is expected to refuse through refuse and to
+// stage what it uploads through a StageRing (k_common.inc), to take the front end of a flat report by day from day_report and
+// its members' words to and from the host from member_copy; forest_passes and the member table (member_table,
+// with_member_table) are for reports that resolve the transmission forest by pointer jumping.
+
+// a member's n_agents elements of `elem` bytes at member * stride of `base`, to the host or from it; waits for the stream
+static int member_copy(const attachment *a, void *base, size_t stride, size_t elem, uint32_t member, void *host, bool to_host, const char *what, hipStream_t s) {
+    if (member >= a->members.size()) return refuse(std::string(what) + ": member out of range");
+    char *dev = static_cast<char *>(base) + (size_t)member * stride * elem;
+    const size_t bytes = elem * a->e0->cfg.n_agents;
+    if (to_host)
+        HIP_CHECK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
+    else
+        HIP_CHECK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return REINA_OK;
+}
+
+// a flat report by day of a log (the dated log's, the course log's)
+struct TxlArgs {
+    AgeGroupArgs p;
+    uint32_t n_days;
+};
+
+// The front end of such a report: the age groups, n_days and the buffer checked in that order under the prefix `what`, the
+// members' blocks of words(n_days) 64-bit words cleared, `a` filled, and the grid of the one launch: four workgroups a compute
+// unit over the tiles (each flushes its LDS tables once).
+static int day_report(const attachment *l, const char *what, uint32_t max_groups, size_t (*words)(uint32_t n_days), const uint8_t *age_group,
+                      uint32_t n_groups, uint32_t n_days, uint64_t *dev_report, hipStream_t s, TxlArgs *a, uint32_t *grid) {
+    if (int rc = age_group_args(l->e0, age_group, n_groups, max_groups, what, &a->p)) return rc;
+    a->n_days = n_days;
+    if (n_days < 1u || n_days > REINA_MAX_DAYS) return refuse(std::string(what) + ": n_days must be in [1, REINA_MAX_DAYS]");
+    if (!dev_report || (reinterpret_cast<uintptr_t>(dev_report) & 15u)) return refuse(std::string(what) + ": the report must be a 16-byte aligned device buffer");
+    const uint32_t K = (uint32_t)l->members.size();
+    HIP_CHECK(hipMemsetAsync(dev_report, 0, words(n_days) * 8u * K, s));
+    *grid = member_grid(l->e0->n_cus, K, (a->p.n_agents + REPORT_TILE - 1u) / REPORT_TILE, 4u);
+    return REINA_OK;
+}
+
+// the passes of a forest report (the tree report's, the lineage report's): links, `rounds` of pointer jumping, a tally, a
+// third pass over the same grid as the tally, and one lane a member to finish
+#define TX_DAY_ROUNDS 13u          // ceil(log2(REINA_MAX_DAYS + 1 + 1)): the most rounds the day word can ask for
+static_assert((1u << (TX_DAY_ROUNDS - 1u)) < REINA_MAX_DAYS + 2u && (1u << TX_DAY_ROUNDS) >= REINA_MAX_DAYS + 2u, "day rounds");
+struct ForestPasses {
+    uint32_t g_links, g_tally, g_jump, rounds;
+};
+static ForestPasses forest_passes(uint32_t N, uint32_t K, uint32_t n_cus, uint32_t host_rounds) {
+    const uint32_t tiles = (N + REPORT_TILE - 1u) / REPORT_TILE, waves = (N + REPORT_THREADS - 1u) / REPORT_THREADS;
+    ForestPasses f;
+    // (four workgroups a compute unit in the passes that flush LDS tables)
+    f.g_links = member_grid(n_cus, K, tiles, 4u);
+    f.g_tally = member_grid(n_cus, K, waves, 4u);
+    f.g_jump = waves < 32768u ? (waves ? waves : 1u) : 32768u;
+    f.rounds = host_rounds != 0xFFFFFFFFu ? host_rounds : TX_DAY_ROUNDS;   // (from the day word: the rounds beyond a member's count return at once)
+    return f;
+}
+
+// a member of a forest report: its state, its scratch and its block of the report
+struct TxMember {
+    const uint32_t *hot;
+    const reina_cold_t *cold;
+    const int32_t *counters;
+    uint64_t *pairs;     // [2][n_agents] (parent | distance << 32)
+    uint32_t *size;      // [n_agents] agents in the tree of each root
+    uint64_t *report;    // [the report's words]
+};
+
+static int tx_engine_ok(const reina_engine_t *e) {
+    if (!e) return REINA_E_INVALID;
+    if (!e->bound) return REINA_E_NOT_BOUND;
+    if (e->cfg.n_shards > 1 || e->exact) return refuse("transmission reports are taken of unsharded engines only");
+    return REINA_OK;
+}
+
+static bool tx_aligned(const void *p) { return p && ((uintptr_t)p & 15u) == 0u; }
+
+static TxMember tx_member_of(const reina_engine_t *e, void *scratch, uint64_t *report) {
+    TxMember m;
+    m.hot = e->buf.hot;
+    m.cold = e->buf.cold;
+    m.counters = e->buf.counters;
+    m.pairs = static_cast<uint64_t *>(scratch);
+    m.size = reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + 16u * (size_t)e->cfg.n_agents);
+    m.report = report;
+    return m;
+}
+
+// A group report's member table on the host: every member checked (`what` names the entry point in the messages), member k
+// with its scratch and block k of `words` words of the report.  Apart from with_member_table: the tree report checks its
+// members before its arguments, the lineage report behind them.
+static int member_table(const std::vector<reina_engine_t *> &members, void *const *dev_scratch, uint64_t *dev_report, size_t words, const char *what,
+                        std::vector<TxMember> *h) {
+    h->resize(members.size());
+    for (size_t k = 0; k < members.size(); k++) {
+        if (int rc = tx_engine_ok(members[k])) return rc;
+        if (!tx_aligned(dev_scratch[k])) return refuse(std::string(what) + ": every member's scratch must be a 16-byte aligned device buffer");
+        (*h)[k] = tx_member_of(members[k], dev_scratch[k], dev_report + k * words);
+    }
+    return REINA_OK;
+}
+
+// ... and on the device around the passes: launch(d_m) with the table uploaded; the table and its host copy live until the
+// passes have run, so the stream is waited for before the table goes
+template <class Launch>
+static int with_member_table(const std::vector<TxMember> &h, const char *what, hipStream_t s, Launch launch) {
+    TxMember *d_m = nullptr;
+    HIP_CHECK(hipMalloc(&d_m, sizeof(TxMember) * h.size()));
+    int rc = REINA_OK;
+    if (hipMemcpyAsync(d_m, h.data(), sizeof(TxMember) * h.size(), hipMemcpyHostToDevice, s) != hipSuccess)
+        rc = refuse(std::string(what) + ": member table upload failed", REINA_E_HIP);
+    if (rc == REINA_OK) rc = launch(d_m);
+    const hipError_t se = hipStreamSynchronize(s);
+    (void)hipFree(d_m);
+    if (rc == REINA_OK && se != hipSuccess) rc = refuse(std::string(what) + ": " + hipGetErrorString(se), REINA_E_HIP);
+    return rc;
 }

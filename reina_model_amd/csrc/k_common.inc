@@ -217,6 +217,83 @@ static_assert(REINA_L_SORT_TICKET < REINA_L_VACC_CURSOR && REINA_L_VACC_CURSOR +
 static thread_local std::string g_last_error;
 static std::atomic<int> g_live_engines{0};   // engines of this process (reina_create .. reina_destroy): who may take the one-launch day (reina_hip.hip)
 
+// The texts these two build from the spelled-out expression (#x) are no part of the library's contract: they change whenever
+// an expression moves.  A refusal with a text of its own goes through refuse, below.
+#define HIP_CHECK(x)                                                                         \
+    do {                                                                                     \
+        hipError_t _e = (x);                                                                 \
+        if (_e != hipSuccess) {                                                              \
+            g_last_error = std::string(#x) + ": " + hipGetErrorString(_e);                   \
+            return REINA_E_HIP;                                                              \
+        }                                                                                    \
+    } while (0)
+#define HIP_CHECK_OR(x, cleanup)                                                             \
+    do {                                                                                     \
+        hipError_t _e = (x);                                                                 \
+        if (_e != hipSuccess) {                                                              \
+            g_last_error = std::string(#x) + ": " + hipGetErrorString(_e);                   \
+            cleanup;                                                                         \
+            return REINA_E_HIP;                                                              \
+        }                                                                                    \
+    } while (0)
+
+// the one way an entry point refuses: the text reina_last_error() gives, and the code
+static int refuse(const std::string &text, int code = REINA_E_INVALID) {
+    g_last_error = text;
+    return code;
+}
+
+// A ring of page-locked blocks of one size, each with the event recorded behind the copy kernel that reads it: what the host
+// writes into a block travels as an ordinary dispatch of the stream, queued behind the work already issued without stalling
+// the host (a pageable source would drain the stream first).  A block is taken again once its copy has left it; while the
+// host runs far ahead of the GPU new blocks are added instead of waiting, up to the caller's cap, and from then on the host
+// waits for block 0.  What is written into a block, and which kernel reads it, is the caller's.
+struct StageRing {
+    std::vector<void *> host;   // hipHostMalloc'd, one a slot
+    std::vector<hipEvent_t> ev;
+    size_t slot = 0;            // the slot acquire handed out last
+
+    int acquire(size_t bytes_per_slot, size_t cap, void **host_ptr, void **device_ptr) {
+        slot = host.size();
+        for (size_t k = 0; k < host.size(); k++)
+            if (hipEventQuery(ev[k]) == hipSuccess) {
+                slot = k;
+                break;
+            }
+        if (slot == host.size()) {
+            if (host.size() < cap) {
+                void *block = nullptr;
+                hipEvent_t e;
+                HIP_CHECK(hipHostMalloc(&block, bytes_per_slot, hipHostMallocDefault));
+                HIP_CHECK_OR(hipEventCreateWithFlags(&e, hipEventDisableTiming), (void)hipHostFree(block));
+                host.push_back(block);
+                ev.push_back(e);
+            } else {
+                slot = 0;
+                HIP_CHECK(hipEventSynchronize(ev[0]));
+            }
+        }
+        *host_ptr = host[slot];
+        HIP_CHECK(hipHostGetDevicePointer(device_ptr, host[slot], 0));
+        return REINA_OK;
+    }
+    // behind the launch that reads the slot
+    int release_behind(hipStream_t s) {
+        HIP_CHECK(hipEventRecord(ev[slot], s));
+        return REINA_OK;
+    }
+    // teardown: every copy has left its block before the block goes
+    void free() {
+        for (size_t k = 0; k < host.size(); k++) {
+            (void)hipEventSynchronize(ev[k]);
+            (void)hipEventDestroy(ev[k]);
+            (void)hipHostFree(host[k]);
+        }
+        host.clear();
+        ev.clear();
+    }
+};
+
 struct reina_engine {
     int32_t init_beds = -1;   // hospital beds passed to reina_init_state (reina_set_initial_state's precondition)
     reina_config_t cfg;
@@ -228,14 +305,9 @@ struct reina_engine {
     MemberRef h_ref;              // the same on the host: a single engine's day kernels take it by value
     DevParams h_params;
     Tables h_tables;
-    // pinned staging ring for table uploads: the copies are queued behind the days already issued
-    // without stalling the host (a pageable source would drain the stream first)
-    // (a slot is reused once its copy has left it; while the host runs far ahead of the GPU new
-    // slots are added instead of waiting, up to MAX_STAGES)
     struct Stage { DevParams p; Tables t; };
     static constexpr size_t MAX_STAGES = 32;
-    std::vector<Stage *> stage;           // hipHostMalloc'd, one per slot
-    std::vector<hipEvent_t> stage_ev;
+    StageRing stage;                        // table uploads (stage_upload): blocks of one Stage
     reina_allreduce_fn coll_fn = nullptr;   // in-stream pressure all-reduce (reina_set_collective)
     void *coll_comm = nullptr;
     reina_alltoall_fn a2a_fn = nullptr;     // in-stream record exchange of exact attribution (reina_set_alltoall)
@@ -256,8 +328,7 @@ struct reina_engine {
     uint32_t *d_bar = nullptr;              // ... its barrier counter, and the barriers passed so far
     uint32_t bar_epoch = 0;
     struct SmallDayRec *d_days = nullptr;   // ... the records of the stretch being run (device), their pinned staging ring
-    std::vector<struct SmallDayRec *> days_stage;
-    std::vector<hipEvent_t> days_stage_ev;
+    StageRing days_stage;
     std::vector<uint32_t> small_pair_days;  // ... days of every timed k_small_days launch (beside kpairs[REINA_PK_SMALL_DAY])
     size_t small_static_lds = 0;            // ... the static LDS of k_small_day (its three phases' functions)
     bool counted_live = false;
@@ -285,15 +356,6 @@ struct reina_engine {
     double k_ms[REINA_PK_NR] = {0};
     uint64_t k_launches[REINA_PK_NR] = {0};
 };
-
-#define HIP_CHECK(x)                                                                         \
-    do {                                                                                     \
-        hipError_t _e = (x);                                                                 \
-        if (_e != hipSuccess) {                                                              \
-            g_last_error = std::string(#x) + ": " + hipGetErrorString(_e);                   \
-            return REINA_E_HIP;                                                              \
-        }                                                                                    \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // small device helpers

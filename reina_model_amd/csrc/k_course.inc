@@ -256,15 +256,7 @@ static void course_detach(reina_course *c) { c->log = nullptr; }
 static int course_live(const reina_course *c) {
     if (!c) return REINA_E_INVALID;
     if (c->log) return REINA_OK;
-    g_last_error = "course: the transmission log it was attached to is gone";
-    return REINA_E_INVALID;
-}
-
-static int course_member(const reina_course *c, uint32_t member) {
-    if (int rc = course_live(c)) return rc;
-    if (member < c->log->members.size()) return REINA_OK;
-    g_last_error = "course: member out of range";
-    return REINA_E_INVALID;
+    return refuse("course: the transmission log it was attached to is gone");
 }
 
 extern "C" {
@@ -274,10 +266,7 @@ int reina_course_version(void) { return REINA_COURSE_VERSION; }
 int reina_course_create(reina_txlog_t *l, void *stream, reina_course_t **out) {
     if (!l || !out) return REINA_E_INVALID;
     if (int rc = attachment_check_members(l->members, "course", "the log it is attached to is")) return rc;
-    if (l->course) {
-        g_last_error = "course: the log has a course attached already";
-        return REINA_E_INVALID;
-    }
+    if (l->course) return refuse("course: the log has a course attached already");
     std::unique_ptr<reina_course, void (*)(reina_course *)> c(new reina_course(), free_course);   // (freed by a failing return)
     hipStream_t s = (hipStream_t)stream;
     const uint32_t N = l->e0->cfg.n_agents, K = (uint32_t)l->members.size();
@@ -301,42 +290,25 @@ int reina_course_report(reina_course_t *course, const uint8_t *age_group, uint32
     reina_txlog *l = course->log;
     hipStream_t s = (hipStream_t)stream;
     TxlArgs a;
-    if (int rc = age_group_args(l->e0, age_group, n_groups, REINA_COURSE_MAX_GROUPS, "course report", &a.p)) return rc;
-    a.n_days = n_days;
-    if (n_days < 1u || n_days > REINA_MAX_DAYS) {
-        g_last_error = "course report: n_days must be in [1, REINA_MAX_DAYS]";
-        return REINA_E_INVALID;
-    }
-    if (!dev_report || (reinterpret_cast<uintptr_t>(dev_report) & 15u)) {
-        g_last_error = "course report: the report must be a 16-byte aligned device buffer";
-        return REINA_E_INVALID;
-    }
+    uint32_t grid;
+    if (int rc = day_report(l, "course report", REINA_COURSE_MAX_GROUPS, [](uint32_t d) -> size_t { return REINA_COURSE_REPORT_WORDS(d); }, age_group, n_groups, n_days,
+                            dev_report, s, &a, &grid))
+        return rc;
     const uint32_t K = (uint32_t)l->members.size();
-    HIP_CHECK(hipMemsetAsync(dev_report, 0, REINA_COURSE_REPORT_WORDS(n_days) * 8u * K, s));
-    // (four workgroups a compute unit: each flushes its LDS tables once)
-    const uint32_t grid = member_grid(l->e0->n_cus, K, (a.p.n_agents + CRS_TILE - 1u) / CRS_TILE, 4u);
     launch_members(k_course_report, l->g, grid, K, CRS_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, course->d_rec, l->stride, dev_report, a);
     return REINA_OK;
 }
 
 int reina_course_read(reina_course_t *course, uint32_t member, uint64_t *out_host, void *stream) {
     if (!out_host) return REINA_E_INVALID;
-    if (int rc = course_member(course, member)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const reina_txlog *l = course->log;
-    HIP_CHECK(hipMemcpyAsync(out_host, course->d_rec + (size_t)member * l->stride, sizeof(crs_rec) * l->e0->cfg.n_agents, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return REINA_OK;
+    if (int rc = course_live(course)) return rc;
+    return member_copy(course->log, course->d_rec, course->log->stride, sizeof(crs_rec), member, out_host, true, "course", (hipStream_t)stream);
 }
 
 int reina_course_write(reina_course_t *course, uint32_t member, const uint64_t *in_host, void *stream) {
     if (!in_host) return REINA_E_INVALID;
-    if (int rc = course_member(course, member)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const reina_txlog *l = course->log;
-    HIP_CHECK(hipMemcpyAsync(course->d_rec + (size_t)member * l->stride, in_host, sizeof(crs_rec) * l->e0->cfg.n_agents, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return REINA_OK;
+    if (int rc = course_live(course)) return rc;
+    return member_copy(course->log, course->d_rec, course->log->stride, sizeof(crs_rec), member, const_cast<uint64_t *>(in_host), false, "course", (hipStream_t)stream);
 }
 
 }  // extern "C"

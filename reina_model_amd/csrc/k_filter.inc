@@ -98,39 +98,24 @@ static int group_clone_pairs(reina_group_t *g, reina_txlog *log, const uint32_t 
     if (!g || g->members.empty()) return REINA_E_INVALID;
     if (n_pairs == 0) return REINA_OK;
     const std::string w(what);
-    if (!pairs) {
-        g_last_error = w + ": no pair list";
-        return REINA_E_INVALID;
-    }
+    if (!pairs) return refuse(w + ": no pair list");
     const uint32_t K = (uint32_t)g->members.size();
     // every check before anything is queued: a refused list leaves every member untouched
     std::vector<uint8_t> role(K, 0);   // bit 0: a destination, bit 1: a source
     for (uint32_t j = 0; j < n_pairs; j++) {
         const uint32_t dst = pairs[2 * j], src = pairs[2 * j + 1];
-        if (dst >= K || src >= K) {
-            g_last_error = w + ": a member index is out of range";
-            return REINA_E_INVALID;
-        }
-        if (role[dst] & 1u) {
-            g_last_error = w + ": a destination appears twice";
-            return REINA_E_INVALID;
-        }
+        if (dst >= K || src >= K) return refuse(w + ": a member index is out of range");
+        if (role[dst] & 1u) return refuse(w + ": a destination appears twice");
         role[dst] |= 1u;
         role[src] |= 2u;
     }
     for (uint32_t m = 0; m < K; m++) {
-        if (role[m] == 3u) {
-            g_last_error = w + ": a source is also a destination";
-            return REINA_E_INVALID;
-        }
+        if (role[m] == 3u) return refuse(w + ": a source is also a destination");
     }
     uint32_t max_queue = g->members[0]->cfg.max_queue;
     for (uint32_t j = 0; j < n_pairs; j++) {
         const reina_engine_t *d = g->members[pairs[2 * j]], *s = g->members[pairs[2 * j + 1]];
-        if (d->testing_ever != s->testing_ever) {
-            g_last_error = w + ": the members' testing_ever flags differ (they ran different plans)";
-            return REINA_E_INVALID;
-        }
+        if (d->testing_ever != s->testing_ever) return refuse(w + ": the members' testing_ever flags differ (they ran different plans)");
     }
     for (auto m : g->members) {
         if (!m->bound) return REINA_E_NOT_BOUND;

@@ -49,15 +49,9 @@ extern "C" {
 int reina_filter_log_version(void) { return REINA_FILTER_LOG_VERSION; }
 
 int reina_group_txlog_clone(reina_txlog_t *log, const uint32_t *pairs, uint32_t n_pairs, void *stream) {
-    if (!log) {
-        g_last_error = "reina_group_txlog_clone: no log";
-        return REINA_E_INVALID;
-    }
+    if (!log) return refuse("reina_group_txlog_clone: no log");
     if (int rc = attachment_kind(log, true, "reina_group_txlog_clone")) return rc;
-    if (log->course && log->course->log != log) {
-        g_last_error = "reina_group_txlog_clone: the course is not attached to this log (its log is gone)";
-        return REINA_E_INVALID;
-    }
+    if (log->course && log->course->log != log) return refuse("reina_group_txlog_clone: the course is not attached to this log (its log is gone)");
     return group_clone_pairs(log->g, log, pairs, n_pairs, stream, "reina_group_txlog_clone");
 }
 

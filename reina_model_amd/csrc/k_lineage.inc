@@ -242,14 +242,8 @@ __global__ __launch_bounds__(64) void k_lineage_finish(const TxMember *M_, const
 
 static int lineage_args(const reina_txlog *l, const uint8_t *age_group, uint32_t n_groups, uint32_t period_days, uint32_t n_periods, uint32_t max_depth,
                         LinArgs *a) {
-    if (period_days < 1u || period_days > REINA_MAX_DAYS) {
-        g_last_error = "lineage report: period_days must be in [1, REINA_MAX_DAYS]";
-        return REINA_E_INVALID;
-    }
-    if (n_periods < 1u || n_periods > REINA_LINEAGE_MAX_PERIODS) {
-        g_last_error = "lineage report: n_periods must be in [1, REINA_LINEAGE_MAX_PERIODS]";
-        return REINA_E_INVALID;
-    }
+    if (period_days < 1u || period_days > REINA_MAX_DAYS) return refuse("lineage report: period_days must be in [1, REINA_MAX_DAYS]");
+    if (n_periods < 1u || n_periods > REINA_LINEAGE_MAX_PERIODS) return refuse("lineage report: n_periods must be in [1, REINA_LINEAGE_MAX_PERIODS]");
     a->period_days = period_days;
     a->P = n_periods;
     a->t.host_rounds = max_depth ? tx_rounds(max_depth) : 0xFFFFFFFFu;
@@ -260,16 +254,11 @@ static int lineage_args(const reina_txlog *l, const uint8_t *age_group, uint32_t
 static int lineage_launch(const reina_txlog *l, const TxMember *d_m, const TxMember &one, const LinArgs &a, uint64_t *report, hipStream_t s) {
     const uint32_t K = (uint32_t)l->members.size(), n_cus = l->e0->n_cus;
     HIP_CHECK(hipMemsetAsync(report, 0, (size_t)K * REINA_LINEAGE_REPORT_WORDS(a.P) * 8u, s));
-    const uint32_t N = a.t.p.n_agents;
-    const uint32_t tiles = (N + TX_TILE - 1u) / TX_TILE, waves = (N + TX_THREADS - 1u) / TX_THREADS;
-    // (four workgroups a compute unit in the passes that flush LDS tables)
-    const uint32_t g_links = member_grid(n_cus, K, tiles, 4u), g_tally = member_grid(n_cus, K, waves, 4u);
-    const uint32_t g_jump = waves < 32768u ? (waves ? waves : 1u) : 32768u;
-    launch_members(k_lineage_links, d_m, g_links, K, TX_THREADS, s, d_m, one, l->d_log, l->stride, a);
-    const uint32_t rounds = a.t.host_rounds != 0xFFFFFFFFu ? a.t.host_rounds : TX_DAY_ROUNDS;
-    for (uint32_t r = 0; r < rounds; r++) launch_members(k_tx_jump, d_m, g_jump, K, TX_THREADS, s, d_m, one, a.t, r);
-    launch_members(k_lineage_tally, d_m, g_tally, K, TX_THREADS, s, d_m, one, l->d_log, l->stride, a);
-    launch_members(k_lineage_roots, d_m, g_tally, K, TX_THREADS, s, d_m, one, l->d_log, l->stride, a);
+    const ForestPasses f = forest_passes(a.t.p.n_agents, K, n_cus, a.t.host_rounds);
+    launch_members(k_lineage_links, d_m, f.g_links, K, TX_THREADS, s, d_m, one, l->d_log, l->stride, a);
+    for (uint32_t r = 0; r < f.rounds; r++) launch_members(k_tx_jump, d_m, f.g_jump, K, TX_THREADS, s, d_m, one, a.t, r);
+    launch_members(k_lineage_tally, d_m, f.g_tally, K, TX_THREADS, s, d_m, one, l->d_log, l->stride, a);
+    launch_members(k_lineage_roots, d_m, f.g_tally, K, TX_THREADS, s, d_m, one, l->d_log, l->stride, a);
     launch_members(k_lineage_finish, d_m, 1u, K, 64, s, d_m, one, a);
     return REINA_OK;
 }
@@ -282,10 +271,7 @@ int reina_lineage_report(reina_txlog_t *log, const uint8_t *age_group, uint32_t 
                          uint32_t max_depth, void *dev_scratch, uint64_t *dev_report, void *stream) {
     if (int rc = attachment_kind(log, false, "reina_lineage_report")) return rc;
     if (int rc = tx_engine_ok(log->e0)) return rc;
-    if (!tx_aligned(dev_scratch) || !tx_aligned(dev_report)) {
-        g_last_error = "reina_lineage_report: scratch and report must be 16-byte aligned device buffers";
-        return REINA_E_INVALID;
-    }
+    if (!tx_aligned(dev_scratch) || !tx_aligned(dev_report)) return refuse("reina_lineage_report: scratch and report must be 16-byte aligned device buffers");
     LinArgs a;
     if (int rc = lineage_args(log, age_group, n_groups, period_days, n_periods, max_depth, &a)) return rc;
     return lineage_launch(log, nullptr, tx_member_of(log->e0, dev_scratch, dev_report), a, dev_report, (hipStream_t)stream);
@@ -295,39 +281,13 @@ int reina_group_lineage_report(reina_txlog_t *log, const uint8_t *age_group, uin
                                uint32_t max_depth, void *const *dev_scratch, uint64_t *dev_report, void *stream) {
     if (int rc = attachment_kind(log, true, "reina_group_lineage_report")) return rc;
     if (!dev_scratch) return REINA_E_INVALID;
-    if (!tx_aligned(dev_report)) {
-        g_last_error = "reina_group_lineage_report: the reports must be a 16-byte aligned device buffer";
-        return REINA_E_INVALID;
-    }
+    if (!tx_aligned(dev_report)) return refuse("reina_group_lineage_report: the reports must be a 16-byte aligned device buffer");
     LinArgs a;
     if (int rc = lineage_args(log, age_group, n_groups, period_days, n_periods, max_depth, &a)) return rc;
-    const uint32_t K = (uint32_t)log->members.size();
-    std::vector<TxMember> h(K);
-    for (uint32_t k = 0; k < K; k++) {
-        if (int rc = tx_engine_ok(log->members[k])) return rc;
-        if (!tx_aligned(dev_scratch[k])) {
-            g_last_error = "reina_group_lineage_report: every member's scratch must be a 16-byte aligned device buffer";
-            return REINA_E_INVALID;
-        }
-        h[k] = tx_member_of(log->members[k], dev_scratch[k], dev_report + (size_t)k * REINA_LINEAGE_REPORT_WORDS(a.P));
-    }
+    std::vector<TxMember> h;
+    if (int rc = member_table(log->members, dev_scratch, dev_report, REINA_LINEAGE_REPORT_WORDS(a.P), "reina_group_lineage_report", &h)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    TxMember *d_m = nullptr;
-    HIP_CHECK(hipMalloc(&d_m, sizeof(TxMember) * K));
-    int rc = REINA_OK;
-    if (hipMemcpyAsync(d_m, h.data(), sizeof(TxMember) * K, hipMemcpyHostToDevice, s) != hipSuccess) {
-        g_last_error = "reina_group_lineage_report: member table upload failed";
-        rc = REINA_E_HIP;
-    }
-    if (rc == REINA_OK) rc = lineage_launch(log, d_m, h[0], a, dev_report, s);
-    // (the member table and its host copy live until the passes have run)
-    const hipError_t se = hipStreamSynchronize(s);
-    (void)hipFree(d_m);
-    if (rc == REINA_OK && se != hipSuccess) {
-        g_last_error = std::string("reina_group_lineage_report: ") + hipGetErrorString(se);
-        rc = REINA_E_HIP;
-    }
-    return rc;
+    return with_member_table(h, "reina_group_lineage_report", s, [&](const TxMember *d_m) { return lineage_launch(log, d_m, h[0], a, dev_report, s); });
 }
 
 }  // extern "C"

@@ -143,35 +143,15 @@ static void free_policy(reina_policy *p) {
 }
 
 static int policy_check_rule(const reina_policy_rule_t *r) {
-    if (r->n_levels < 2u || r->n_levels > REINA_POLICY_MAX_LEVELS) {
-        g_last_error = "policy: n_levels must be in [2, REINA_POLICY_MAX_LEVELS]";
-        return REINA_E_INVALID;
-    }
-    if (r->signal >= REINA_C_NR) {
-        g_last_error = "policy: signal is not a per-age counter row (REINA_C_*)";
-        return REINA_E_INVALID;
-    }
-    if (r->kind != REINA_POLICY_LEVEL && r->kind != REINA_POLICY_INCREMENT) {
-        g_last_error = "policy: kind must be REINA_POLICY_LEVEL or REINA_POLICY_INCREMENT";
-        return REINA_E_INVALID;
-    }
-    if (r->kind == REINA_POLICY_INCREMENT && (r->n_days < 1u || r->n_days > 28u)) {
-        g_last_error = "policy: an increment is taken over 1..28 days";
-        return REINA_E_INVALID;
-    }
-    if (r->review_every < 1u) {
-        g_last_error = "policy: review_every must be at least 1";
-        return REINA_E_INVALID;
-    }
-    if (r->start_day >= REINA_MAX_DAYS) {
-        g_last_error = "policy: start_day >= REINA_MAX_DAYS";
-        return REINA_E_INVALID;
-    }
+    if (r->n_levels < 2u || r->n_levels > REINA_POLICY_MAX_LEVELS) return refuse("policy: n_levels must be in [2, REINA_POLICY_MAX_LEVELS]");
+    if (r->signal >= REINA_C_NR) return refuse("policy: signal is not a per-age counter row (REINA_C_*)");
+    if (r->kind != REINA_POLICY_LEVEL && r->kind != REINA_POLICY_INCREMENT) return refuse("policy: kind must be REINA_POLICY_LEVEL or REINA_POLICY_INCREMENT");
+    if (r->kind == REINA_POLICY_INCREMENT && (r->n_days < 1u || r->n_days > 28u)) return refuse("policy: an increment is taken over 1..28 days");
+    if (r->review_every < 1u) return refuse("policy: review_every must be at least 1");
+    if (r->start_day >= REINA_MAX_DAYS) return refuse("policy: start_day >= REINA_MAX_DAYS");
     for (uint32_t j = 0; j + 1u < r->n_levels; j++)
-        if ((j > 0 && r->up[j] < r->up[j - 1]) || r->down[j] > r->up[j]) {
-            g_last_error = "policy: inconsistent thresholds (up[] must be non-decreasing and down[j] <= up[j])";
-            return REINA_E_INVALID;
-        }
+        if ((j > 0 && r->up[j] < r->up[j - 1]) || r->down[j] > r->up[j])
+            return refuse("policy: inconsistent thresholds (up[] must be non-decreasing and down[j] <= up[j])");
     return REINA_OK;
 }
 
@@ -218,10 +198,7 @@ static int policy_launch_day(attachment *a, const reina_day_t &dp, hipStream_t s
 static int policy_begin_run(reina_policy *p) {
     uint32_t rows = 0, crows = 0;
     for (uint32_t l = 0; l < p->rule.n_levels; l++) {
-        if (!p->uploaded[l]) {
-            g_last_error = "policy: bank level " + std::to_string(l) + " was never uploaded";
-            return REINA_E_INVALID;
-        }
+        if (!p->uploaded[l]) return refuse("policy: bank level " + std::to_string(l) + " was never uploaded");
         if (p->h_bank[l].t.n_rows > rows) rows = p->h_bank[l].t.n_rows;
         if (p->h_bank[l].t.n_crows > crows) crows = p->h_bank[l].t.n_crows;
     }
@@ -232,10 +209,7 @@ static int policy_begin_run(reina_policy *p) {
 // before a run: every day has its trace words (refused as a whole, before any of its days is queued)
 static int policy_check_days(const reina_day_t *days, uint32_t n_days) {
     for (uint32_t k = 0; k < n_days; k++)
-        if (days[k].day >= REINA_MAX_DAYS) {
-            g_last_error = "policy: day >= REINA_MAX_DAYS (4096): the trace has no words for it";
-            return REINA_E_INVALID;
-        }
+        if (days[k].day >= REINA_MAX_DAYS) return refuse("policy: day >= REINA_MAX_DAYS (4096): the trace has no words for it");
     return REINA_OK;
 }
 static void policy_end_run(reina_policy *p) { p->e0->policy_lds_rows = p->e0->policy_lds_crows = 0; }
@@ -261,10 +235,7 @@ int reina_policy_destroy(reina_policy_t *p) {
 
 int reina_policy_upload_level(reina_policy_t *p, uint32_t level, const reina_contact_tables_t *t, void *stream) {
     if (!p || !t) return REINA_E_INVALID;
-    if (level >= p->rule.n_levels) {
-        g_last_error = "policy: level out of range";
-        return REINA_E_INVALID;
-    }
+    if (level >= p->rule.n_levels) return refuse("policy: level out of range");
     PolicyEntry &E = p->h_bank[level];
     if (int rc = derive_contact_tables(p->e0, t, E.p, E.t)) return rc;
     if (int rc = stage_upload(p->e0, E.p, E.t, &p->d_bank[level].p, &p->d_bank[level].t, (hipStream_t)stream)) return rc;
@@ -295,14 +266,8 @@ int reina_group_policy_run_days(reina_policy_t *p, const reina_day_t *days, uint
 
 int reina_policy_read_trace(reina_policy_t *p, uint32_t first_day, uint32_t n_days, int32_t *out_host, void *stream) {
     if (!p) return REINA_E_INVALID;
-    if (n_days && !out_host) {
-        g_last_error = "policy: read_trace without an output buffer (out_host is null)";
-        return REINA_E_INVALID;
-    }
-    if ((uint64_t)first_day + n_days > REINA_MAX_DAYS) {
-        g_last_error = "policy: trace range beyond REINA_MAX_DAYS";
-        return REINA_E_INVALID;
-    }
+    if (n_days && !out_host) return refuse("policy: read_trace without an output buffer (out_host is null)");
+    if ((uint64_t)first_day + n_days > REINA_MAX_DAYS) return refuse("policy: trace range beyond REINA_MAX_DAYS");
     hipStream_t s = (hipStream_t)stream;
     const size_t K = p->members.size(), day_bytes = sizeof(int32_t) * REINA_POLICY_TRACE_WORDS;
     if (n_days)

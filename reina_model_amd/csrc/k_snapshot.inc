@@ -279,10 +279,7 @@ static uint64_t snap_fnv1a(const void *p, size_t n) {
 static int snap_engine_ok(const reina_engine_t *e) {
     if (!e) return REINA_E_INVALID;
     if (!e->bound) return REINA_E_NOT_BOUND;
-    if (e->cfg.n_shards > 1 || e->exact) {
-        g_last_error = "snapshots are taken of, and restored into, unsharded engines only";
-        return REINA_E_INVALID;
-    }
+    if (e->cfg.n_shards > 1 || e->exact) return refuse("snapshots are taken of, and restored into, unsharded engines only");
     return REINA_OK;
 }
 
@@ -314,27 +311,20 @@ static void snap_header(const reina_engine_t *e, uint32_t n_base, uint32_t n_slo
 // an image's header against engine `e`: the same population, variants and disease, counts within the engine's buffers
 static int snap_validate(const reina_engine_t *e, const uint32_t *h, SnapLayout *l) {
     if (int rc = snap_engine_ok(e)) return rc;
-    const char *why = nullptr;
     const uint32_t N = e->cfg.n_agents;
     const uint32_t qlen[3] = {h[REINA_SNAP_H_LEN_Q0], h[REINA_SNAP_H_LEN_Q1], h[REINA_SNAP_H_LEN_L1]};
-    if (h[REINA_SNAP_H_MAGIC] != REINA_SNAP_MAGIC) why = "not a snapshot image (magic)";
-    else if (h[REINA_SNAP_H_VERSION] != REINA_SNAPSHOT_VERSION) why = "snapshot format version differs from the library's";
-    else if (h[REINA_SNAP_H_N_AGENTS] != N || h[REINA_SNAP_H_NR_AGES] != e->cfg.nr_ages) why = "snapshot of another population";
-    else if (h[REINA_SNAP_H_NR_VARIANTS] != e->cfg.nr_variants) why = "snapshot with another number of variants";
-    else if (h[REINA_SNAP_H_N_BASE] > N || h[REINA_SNAP_H_N_SLOT] > h[REINA_SNAP_H_N_BASE]) why = "snapshot record counts out of range";
-    else if (qlen[0] > e->cfg.max_queue || qlen[1] > e->cfg.max_queue || qlen[2] > e->cfg.max_queue) why = "snapshot queue longer than the engine's queues";
-    if (!why) {
-        uint32_t want[REINA_SNAP_HEADER_WORDS];
-        snap_header(e, h[REINA_SNAP_H_N_BASE], h[REINA_SNAP_H_N_SLOT], qlen, want);
-        if (std::memcmp(&h[REINA_SNAP_H_AGES_HASH], &want[REINA_SNAP_H_AGES_HASH], 8) != 0) why = "snapshot of another population (age structure)";
-        else if (std::memcmp(&h[REINA_SNAP_H_DISEASE_HASH], &want[REINA_SNAP_H_DISEASE_HASH], 8) != 0) why = "snapshot of another disease";
-        else if (h[REINA_SNAP_H_N_TILES] != want[REINA_SNAP_H_N_TILES] || h[REINA_SNAP_H_BYTES] != want[REINA_SNAP_H_BYTES] ||
-                 h[REINA_SNAP_H_BYTES + 1] != want[REINA_SNAP_H_BYTES + 1]) why = "snapshot image size does not match its header";
-    }
-    if (why) {
-        g_last_error = why;
-        return REINA_E_INVALID;
-    }
+    if (h[REINA_SNAP_H_MAGIC] != REINA_SNAP_MAGIC) return refuse("not a snapshot image (magic)");
+    if (h[REINA_SNAP_H_VERSION] != REINA_SNAPSHOT_VERSION) return refuse("snapshot format version differs from the library's");
+    if (h[REINA_SNAP_H_N_AGENTS] != N || h[REINA_SNAP_H_NR_AGES] != e->cfg.nr_ages) return refuse("snapshot of another population");
+    if (h[REINA_SNAP_H_NR_VARIANTS] != e->cfg.nr_variants) return refuse("snapshot with another number of variants");
+    if (h[REINA_SNAP_H_N_BASE] > N || h[REINA_SNAP_H_N_SLOT] > h[REINA_SNAP_H_N_BASE]) return refuse("snapshot record counts out of range");
+    if (qlen[0] > e->cfg.max_queue || qlen[1] > e->cfg.max_queue || qlen[2] > e->cfg.max_queue) return refuse("snapshot queue longer than the engine's queues");
+    uint32_t want[REINA_SNAP_HEADER_WORDS];
+    snap_header(e, h[REINA_SNAP_H_N_BASE], h[REINA_SNAP_H_N_SLOT], qlen, want);
+    if (std::memcmp(&h[REINA_SNAP_H_AGES_HASH], &want[REINA_SNAP_H_AGES_HASH], 8) != 0) return refuse("snapshot of another population (age structure)");
+    if (std::memcmp(&h[REINA_SNAP_H_DISEASE_HASH], &want[REINA_SNAP_H_DISEASE_HASH], 8) != 0) return refuse("snapshot of another disease");
+    if (h[REINA_SNAP_H_N_TILES] != want[REINA_SNAP_H_N_TILES] || h[REINA_SNAP_H_BYTES] != want[REINA_SNAP_H_BYTES] || h[REINA_SNAP_H_BYTES + 1] != want[REINA_SNAP_H_BYTES + 1])
+        return refuse("snapshot image size does not match its header");
     *l = snap_layout(N, h[REINA_SNAP_H_N_BASE], h[REINA_SNAP_H_N_SLOT], qlen);
     return REINA_OK;
 }
@@ -385,10 +375,7 @@ int reina_snap_measure(reina_engine_t *e, uint64_t *bytes, void *stream) {
     HIP_CHECK(hipMemcpyAsync(qlen, e->buf.control + REINA_L_QUEUE0, sizeof(qlen), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     for (int k = 0; k < 3; k++) {
-        if (qlen[k] < 0 || (uint32_t)qlen[k] > e->cfg.max_queue) {
-            g_last_error = "a queue length of the control block is out of range";
-            return REINA_E_INVALID;
-        }
+        if (qlen[k] < 0 || (uint32_t)qlen[k] > e->cfg.max_queue) return refuse("a queue length of the control block is out of range");
         e->snap_qlen[k] = (uint32_t)qlen[k];
     }
     e->snap_total[0] = tot[0];
@@ -398,16 +385,10 @@ int reina_snap_measure(reina_engine_t *e, uint64_t *bytes, void *stream) {
 }
 
 int reina_snap_pack(reina_engine_t *e, void *dev_out, uint64_t cap, void *stream) {
-    if (!dev_out || ((uintptr_t)dev_out & 15u)) {
-        g_last_error = "reina_snap_pack: the output must be a 16-byte aligned device buffer";
-        return REINA_E_INVALID;
-    }
+    if (!dev_out || ((uintptr_t)dev_out & 15u)) return refuse("reina_snap_pack: the output must be a 16-byte aligned device buffer");
     uint64_t bytes = 0;
     if (int rc = reina_snap_measure(e, &bytes, stream)) return rc;
-    if (cap < bytes) {
-        g_last_error = "reina_snap_pack: output buffer smaller than the measured image";
-        return REINA_E_INVALID;
-    }
+    if (cap < bytes) return refuse("reina_snap_pack: output buffer smaller than the measured image");
     hipStream_t s = (hipStream_t)stream;
     const uint32_t N = e->cfg.n_agents;
     const SnapLayout l = snap_layout(N, e->snap_total[0], e->snap_total[1], e->snap_qlen);
@@ -434,10 +415,7 @@ int reina_snap_pack(reina_engine_t *e, void *dev_out, uint64_t cap, void *stream
 
 int reina_snap_unpack(reina_engine_t *e, const void *dev_in, void *stream) {
     if (int rc = snap_engine_ok(e)) return rc;
-    if (!dev_in || ((uintptr_t)dev_in & 15u)) {
-        g_last_error = "reina_snap_unpack: the image must be a 16-byte aligned device buffer";
-        return REINA_E_INVALID;
-    }
+    if (!dev_in || ((uintptr_t)dev_in & 15u)) return refuse("reina_snap_unpack: the image must be a 16-byte aligned device buffer");
     hipStream_t s = (hipStream_t)stream;
     uint32_t h[REINA_SNAP_HEADER_WORDS];
     if (int rc = snap_read_header(dev_in, h, s)) return rc;
@@ -453,10 +431,7 @@ int reina_snap_unpack(reina_engine_t *e, const void *dev_in, void *stream) {
 
 int reina_group_snap_unpack(reina_group_t *g, const void *dev_in, void *stream) {
     if (!g || g->members.empty()) return REINA_E_INVALID;
-    if (!dev_in || ((uintptr_t)dev_in & 15u)) {
-        g_last_error = "reina_group_snap_unpack: the image must be a 16-byte aligned device buffer";
-        return REINA_E_INVALID;
-    }
+    if (!dev_in || ((uintptr_t)dev_in & 15u)) return refuse("reina_group_snap_unpack: the image must be a 16-byte aligned device buffer");
     hipStream_t s = (hipStream_t)stream;
     uint32_t h[REINA_SNAP_HEADER_WORDS];
     if (int rc = snap_read_header(dev_in, h, s)) return rc;

@@ -197,48 +197,20 @@ __global__ __launch_bounds__(SUM_THREADS) void k_summary_order(const SumHead *he
 // ---------------------------------------------------------------------------------------------
 // host side
 
-// page-locked slots the head is written to before k_summary_head copies it: process-wide (a summary has no engine), each
-// free again when the event recorded behind its copy has passed
-struct SumStage {
-    void *host = nullptr;
-    hipEvent_t ev = nullptr;
-};
+// page-locked blocks the head is written to before k_summary_head copies it: one ring for the process (a summary has no engine)
 static std::mutex g_sum_stage_mu;
-static std::vector<SumStage> g_sum_stages;
+static StageRing g_sum_stages;
 static const size_t SUM_MAX_STAGES = 8;
 
 static int summary_stage(const void *head, size_t bytes, void *dst, hipStream_t s) {
     std::lock_guard<std::mutex> lock(g_sum_stage_mu);
-    size_t slot = g_sum_stages.size();
-    for (size_t k = 0; k < g_sum_stages.size(); k++)
-        if (hipEventQuery(g_sum_stages[k].ev) == hipSuccess) {
-            slot = k;
-            break;
-        }
-    if (slot == g_sum_stages.size()) {
-        if (g_sum_stages.size() < SUM_MAX_STAGES) {
-            SumStage st;
-            HIP_CHECK(hipHostMalloc(&st.host, REINA_SUMMARY_HEAD_BYTES(REINA_SUMMARY_MAX_MEMBERS), hipHostMallocDefault));
-            HIP_CHECK_OR(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming), (void)hipHostFree(st.host));
-            g_sum_stages.push_back(st);
-        } else {
-            slot = 0;
-            HIP_CHECK(hipEventSynchronize(g_sum_stages[0].ev));
-        }
-    }
-    std::memcpy(g_sum_stages[slot].host, head, bytes);
-    void *dsrc = nullptr;
-    HIP_CHECK(hipHostGetDevicePointer(&dsrc, g_sum_stages[slot].host, 0));
+    void *block = nullptr, *dsrc = nullptr;
+    if (int rc = g_sum_stages.acquire(REINA_SUMMARY_HEAD_BYTES(REINA_SUMMARY_MAX_MEMBERS), SUM_MAX_STAGES, &block, &dsrc)) return rc;
+    std::memcpy(block, head, bytes);
     const uint32_t n = (uint32_t)(bytes / 8u);
     hipLaunchKernelGGL(k_summary_head, dim3((n + SUM_THREADS - 1u) / SUM_THREADS), dim3(SUM_THREADS), 0, s, (uint64_t *)dst, (const uint64_t *)dsrc, n);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(g_sum_stages[slot].ev, s));
-    return REINA_OK;
-}
-
-static int summary_refuse(const char *why) {
-    g_last_error = std::string("reina_summary: ") + why;
-    return REINA_E_INVALID;
+    return g_sum_stages.release_behind(s);
 }
 
 extern "C" {
@@ -248,34 +220,34 @@ int reina_summary_version(void) { return REINA_SUMMARY_VERSION; }
 int reina_summary(const int32_t *const *history_bases, uint32_t K, uint32_t days, uint32_t nr_ages, const uint8_t *age_group, uint32_t n_groups,
                   const uint32_t *ranks, uint32_t n_ranks, const reina_summary_threshold_t *thresholds, uint32_t n_thresholds, void *dev_scratch,
                   int64_t *dev_report, void *stream) {
-    if (K < 1u || K > REINA_SUMMARY_MAX_MEMBERS) return summary_refuse("K must be in [1, REINA_SUMMARY_MAX_MEMBERS]");
-    if (days < 1u || days > REINA_MAX_DAYS) return summary_refuse("days must be in [1, REINA_MAX_DAYS]");
-    if (nr_ages < 1u || nr_ages > REINA_MAX_AGES) return summary_refuse("nr_ages must be in [1, REINA_MAX_AGES]");
-    if (n_groups < 1u || n_groups > REINA_SUMMARY_MAX_GROUPS) return summary_refuse("n_groups must be in [1, REINA_SUMMARY_MAX_GROUPS]");
-    if (n_ranks > REINA_SUMMARY_MAX_RANKS) return summary_refuse("n_ranks must be at most REINA_SUMMARY_MAX_RANKS");
-    if (n_thresholds > REINA_SUMMARY_MAX_THRESHOLDS) return summary_refuse("n_thresholds must be at most REINA_SUMMARY_MAX_THRESHOLDS");
+    if (K < 1u || K > REINA_SUMMARY_MAX_MEMBERS) return refuse("reina_summary: K must be in [1, REINA_SUMMARY_MAX_MEMBERS]");
+    if (days < 1u || days > REINA_MAX_DAYS) return refuse("reina_summary: days must be in [1, REINA_MAX_DAYS]");
+    if (nr_ages < 1u || nr_ages > REINA_MAX_AGES) return refuse("reina_summary: nr_ages must be in [1, REINA_MAX_AGES]");
+    if (n_groups < 1u || n_groups > REINA_SUMMARY_MAX_GROUPS) return refuse("reina_summary: n_groups must be in [1, REINA_SUMMARY_MAX_GROUPS]");
+    if (n_ranks > REINA_SUMMARY_MAX_RANKS) return refuse("reina_summary: n_ranks must be at most REINA_SUMMARY_MAX_RANKS");
+    if (n_thresholds > REINA_SUMMARY_MAX_THRESHOLDS) return refuse("reina_summary: n_thresholds must be at most REINA_SUMMARY_MAX_THRESHOLDS");
     if (!history_bases || !age_group || (n_ranks && !ranks) || (n_thresholds && !thresholds) || !dev_scratch || !dev_report)
-        return summary_refuse("null pointer");
-    if (((uintptr_t)dev_scratch & 15u) || ((uintptr_t)dev_report & 15u)) return summary_refuse("scratch and report must be 16-byte aligned device buffers");
+        return refuse("reina_summary: null pointer");
+    if (((uintptr_t)dev_scratch & 15u) || ((uintptr_t)dev_report & 15u)) return refuse("reina_summary: scratch and report must be 16-byte aligned device buffers");
     const uint32_t S = REINA_SUMMARY_SERIES(n_groups);
     std::vector<uint64_t> block(REINA_SUMMARY_HEAD_BYTES(K) / 8u, 0ull);
     SumHead *h = reinterpret_cast<SumHead *>(block.data());
     for (uint32_t k = 0; k < nr_ages; k++) {
-        if (age_group[k] >= n_groups) return summary_refuse("an age's group is not below n_groups");
+        if (age_group[k] >= n_groups) return refuse("reina_summary: an age's group is not below n_groups");
         h->group[k] = age_group[k];
     }
     for (uint32_t q = 0; q < n_ranks; q++) {
-        if (ranks[q] >= K) return summary_refuse("a rank is not below K");
+        if (ranks[q] >= K) return refuse("reina_summary: a rank is not below K");
         h->ranks[q] = ranks[q];
     }
     for (uint32_t t = 0; t < n_thresholds; t++) {
-        if (thresholds[t].series >= S) return summary_refuse("a threshold's series is not below S");
+        if (thresholds[t].series >= S) return refuse("reina_summary: a threshold's series is not below S");
         h->thr_series[t] = thresholds[t].series;
         h->thr_value[t] = thresholds[t].value;
     }
     for (uint32_t m = 0; m < K; m++) {
-        if (!history_bases[m]) return summary_refuse("null pointer (a member's rows)");
-        if ((uintptr_t)history_bases[m] & 15u) return summary_refuse("every member's rows must be 16-byte aligned");
+        if (!history_bases[m]) return refuse("reina_summary: null pointer (a member's rows)");
+        if ((uintptr_t)history_bases[m] & 15u) return refuse("reina_summary: every member's rows must be 16-byte aligned");
         block[sizeof(SumHead) / 8u + m] = (uint64_t)(uintptr_t)history_bases[m];
     }
     // (every pass is one workgroup a unit of work: the grids follow the shapes, not the chip's compute units)

@@ -1,6 +1,7 @@
 // reina_hip.hip part: transmission-tree reports of an unsharded engine between two days (include/reina_transmission.h;
 // DESIGN.md "Transmission reports").  Included at the end of reina_hip.hip (it uses the host helpers, the group and
-// k_addons.inc above: the wave helpers, load_links, the age-group arguments and the launch geometry).
+// k_addons.inc above: the wave helpers, load_links, the age-group arguments, the launch geometry, and TxMember with the
+// passes and member table a forest report shares with the lineage report).
 //
 // A report reads the hot words and the cold records and writes nothing but the caller's scratch and report block.  Five kinds
 // of launch, each bound by memory bandwidth:
@@ -26,22 +27,11 @@
 #define TX_DIST_MAX 0x7FFFFFFFu    // distances saturate (a cycle of bad data doubles them every round)
 #define TX_HASH 4096u              // k_tx_tally's LDS hash slots
 #define TX_HASH_PROBES 8
-#define TX_DAY_ROUNDS 13u          // ceil(log2(REINA_MAX_DAYS + 1 + 1)): the most rounds the day word can ask for
 #define TX_CELLS (REINA_TX_VARIANTS * REINA_TX_SEVERITIES * REINA_TX_OUTCOMES * 2u * REINA_TX_BINS)
 #define TX_MATRIX_CELLS (REINA_TX_VARIANTS * REINA_TX_MAX_GROUPS * REINA_TX_MAX_GROUPS)
 #define TX_SUMS (REINA_TX_VARIANTS * REINA_TX_OUTCOMES)
 static_assert(REINA_TX_OFFSPRING_SUM == TX_CELLS && REINA_TX_REPORT_WORDS == 9834u, "report layout");
 static_assert(REINA_MAX_VARIANTS == REINA_TX_VARIANTS, "RH_VARIANT has two bits");
-static_assert((1u << (TX_DAY_ROUNDS - 1u)) < REINA_MAX_DAYS + 2u && (1u << TX_DAY_ROUNDS) >= REINA_MAX_DAYS + 2u, "day rounds");
-
-struct TxMember {
-    const uint32_t *hot;
-    const reina_cold_t *cold;
-    const int32_t *counters;
-    uint64_t *pairs;     // [2][n_agents] (parent | distance << 32)
-    uint32_t *size;      // [n_agents] agents in the tree of each root
-    uint64_t *report;    // [REINA_TX_REPORT_WORDS]
-};
 
 struct TxArgs {
     AgeGroupArgs p;
@@ -288,47 +278,19 @@ __global__ __launch_bounds__(64) void k_tx_finish(const TxMember *M_, const TxMe
 // ---------------------------------------------------------------------------------------------
 // host side
 
-static int tx_engine_ok(const reina_engine_t *e) {
-    if (!e) return REINA_E_INVALID;
-    if (!e->bound) return REINA_E_NOT_BOUND;
-    if (e->cfg.n_shards > 1 || e->exact) {
-        g_last_error = "transmission reports are taken of unsharded engines only";
-        return REINA_E_INVALID;
-    }
-    return REINA_OK;
-}
-
 static int tx_args(const reina_engine_t *e, const uint8_t *age_group, uint32_t n_groups, uint32_t max_depth, TxArgs *a) {
     a->host_rounds = max_depth ? tx_rounds(max_depth) : 0xFFFFFFFFu;
     return age_group_args(e, age_group, n_groups, REINA_TX_MAX_GROUPS, "reina_tx_report", &a->p);
 }
 
-static bool tx_aligned(const void *p) { return p && ((uintptr_t)p & 15u) == 0u; }
-
-static TxMember tx_member_of(const reina_engine_t *e, void *scratch, uint64_t *report) {
-    TxMember m;
-    m.hot = e->buf.hot;
-    m.cold = e->buf.cold;
-    m.counters = e->buf.counters;
-    m.pairs = static_cast<uint64_t *>(scratch);
-    m.size = reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + 16u * (size_t)e->cfg.n_agents);
-    m.report = report;
-    return m;
-}
-
 // every pass of a report: the K members of the device table `d_m`, or (d_m = nullptr) the one member `one`
 static int tx_launch(const TxMember *d_m, const TxMember &one, const TxArgs &a, uint32_t K, uint32_t n_cus, uint64_t *report, hipStream_t s) {
     HIP_CHECK(hipMemsetAsync(report, 0, (size_t)K * REINA_TX_REPORT_WORDS * 8u, s));
-    const uint32_t N = a.p.n_agents;
-    const uint32_t tiles = (N + TX_TILE - 1u) / TX_TILE, waves = (N + TX_THREADS - 1u) / TX_THREADS;
-    // (four workgroups a compute unit in the passes that flush LDS tables)
-    const uint32_t g_links = member_grid(n_cus, K, tiles, 4u), g_tally = member_grid(n_cus, K, waves, 4u);
-    const uint32_t g_jump = waves < 32768u ? (waves ? waves : 1u) : 32768u;
-    launch_members(k_tx_links, d_m, g_links, K, TX_THREADS, s, d_m, one, a);
-    const uint32_t rounds = a.host_rounds != 0xFFFFFFFFu ? a.host_rounds : TX_DAY_ROUNDS;
-    for (uint32_t r = 0; r < rounds; r++) launch_members(k_tx_jump, d_m, g_jump, K, TX_THREADS, s, d_m, one, a, r);
-    launch_members(k_tx_tally, d_m, g_tally, K, TX_THREADS, s, d_m, one, a);
-    launch_members(k_tx_clusters, d_m, g_tally, K, TX_THREADS, s, d_m, one, a);
+    const ForestPasses f = forest_passes(a.p.n_agents, K, n_cus, a.host_rounds);
+    launch_members(k_tx_links, d_m, f.g_links, K, TX_THREADS, s, d_m, one, a);
+    for (uint32_t r = 0; r < f.rounds; r++) launch_members(k_tx_jump, d_m, f.g_jump, K, TX_THREADS, s, d_m, one, a, r);
+    launch_members(k_tx_tally, d_m, f.g_tally, K, TX_THREADS, s, d_m, one, a);
+    launch_members(k_tx_clusters, d_m, f.g_tally, K, TX_THREADS, s, d_m, one, a);
     launch_members(k_tx_finish, d_m, 1u, K, 64, s, d_m, one, a);
     return REINA_OK;
 }
@@ -340,10 +302,7 @@ int reina_tx_version(void) { return REINA_TX_VERSION; }
 int reina_tx_report(reina_engine_t *e, const uint8_t *age_group, uint32_t n_groups, uint32_t max_depth, void *dev_scratch,
                     uint64_t *dev_report, void *stream) {
     if (int rc = tx_engine_ok(e)) return rc;
-    if (!tx_aligned(dev_scratch) || !tx_aligned(dev_report)) {
-        g_last_error = "reina_tx_report: scratch and report must be 16-byte aligned device buffers";
-        return REINA_E_INVALID;
-    }
+    if (!tx_aligned(dev_scratch) || !tx_aligned(dev_report)) return refuse("reina_tx_report: scratch and report must be 16-byte aligned device buffers");
     TxArgs a;
     if (int rc = tx_args(e, age_group, n_groups, max_depth, &a)) return rc;
     return tx_launch(nullptr, tx_member_of(e, dev_scratch, dev_report), a, 1u, e->n_cus, dev_report, (hipStream_t)stream);
@@ -352,39 +311,15 @@ int reina_tx_report(reina_engine_t *e, const uint8_t *age_group, uint32_t n_grou
 int reina_group_tx_report(reina_group_t *g, const uint8_t *age_group, uint32_t n_groups, uint32_t max_depth,
                           void *const *dev_scratch, uint64_t *dev_report, void *stream) {
     if (!g || g->members.empty() || !dev_scratch) return REINA_E_INVALID;
-    if (!tx_aligned(dev_report)) {
-        g_last_error = "reina_group_tx_report: the reports must be a 16-byte aligned device buffer";
-        return REINA_E_INVALID;
-    }
-    const uint32_t K = (uint32_t)g->members.size();
-    std::vector<TxMember> h(K);
-    for (uint32_t k = 0; k < K; k++) {
-        if (int rc = tx_engine_ok(g->members[k])) return rc;
-        if (!tx_aligned(dev_scratch[k])) {
-            g_last_error = "reina_group_tx_report: every member's scratch must be a 16-byte aligned device buffer";
-            return REINA_E_INVALID;
-        }
-        h[k] = tx_member_of(g->members[k], dev_scratch[k], dev_report + (size_t)k * REINA_TX_REPORT_WORDS);
-    }
+    if (!tx_aligned(dev_report)) return refuse("reina_group_tx_report: the reports must be a 16-byte aligned device buffer");
+    std::vector<TxMember> h;
+    if (int rc = member_table(g->members, dev_scratch, dev_report, REINA_TX_REPORT_WORDS, "reina_group_tx_report", &h)) return rc;
     TxArgs a;
     if (int rc = tx_args(g->members[0], age_group, n_groups, max_depth, &a)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    TxMember *d_m = nullptr;
-    HIP_CHECK(hipMalloc(&d_m, sizeof(TxMember) * K));
-    int rc = REINA_OK;
-    if (hipMemcpyAsync(d_m, h.data(), sizeof(TxMember) * K, hipMemcpyHostToDevice, s) != hipSuccess) {
-        g_last_error = "reina_group_tx_report: member table upload failed";
-        rc = REINA_E_HIP;
-    }
-    if (rc == REINA_OK) rc = tx_launch(d_m, h[0], a, K, g->members[0]->n_cus, dev_report, s);
-    // (the member table and its host copy live until the passes have run)
-    const hipError_t se = hipStreamSynchronize(s);
-    (void)hipFree(d_m);
-    if (rc == REINA_OK && se != hipSuccess) {
-        g_last_error = std::string("reina_group_tx_report: ") + hipGetErrorString(se);
-        rc = REINA_E_HIP;
-    }
-    return rc;
+    return with_member_table(h, "reina_group_tx_report", s, [&](const TxMember *d_m) {
+        return tx_launch(d_m, h[0], a, (uint32_t)h.size(), g->members[0]->n_cus, dev_report, s);
+    });
 }
 
 }  // extern "C"

@@ -31,11 +31,6 @@ static_assert(REINA_MAX_DAYS < REINA_TXLOG_BEFORE, "day numbers lie below the co
 static_assert(REINA_TXLOG_FIXED_WORDS == 1312u && REINA_TXLOG_DAY_WORDS == 80u, "report layout");
 static_assert(REINA_TXLOG_VARIANTS == REINA_MAX_VARIANTS && REINA_TXLOG_MAX_GROUPS == REINA_TX_MAX_GROUPS, "RH_VARIANT has two bits; the groups are the tree reports'");
 
-struct TxlArgs {
-    AgeGroupArgs p;
-    uint32_t n_days;
-};
-
 __host__ __device__ __forceinline__ uint32_t txl_begin_word(uint32_t w) {
     const uint32_t st = RH_STATE(w);
     return (st >= RS_ILLNESS ? TXL_BEFORE : TXL_NONE) << 16 | (st != RS_SUSCEPTIBLE ? TXL_BEFORE : TXL_NONE);
@@ -236,10 +231,7 @@ static int txlog_create(const std::vector<reina_engine_t *> &members, reina_grou
     if (!out) return REINA_E_INVALID;
     if (int rc = attachment_check_members(members, "txlog", "links are global ids, and a shard sees only its own agents' onsets")) return rc;
     for (auto m : members)
-        if (reinterpret_cast<uintptr_t>(m->buf.hot) & 15u) {
-            g_last_error = "txlog: the hot words must be 16-byte aligned";
-            return REINA_E_INVALID;
-        }
+        if (reinterpret_cast<uintptr_t>(m->buf.hot) & 15u) return refuse("txlog: the hot words must be 16-byte aligned");
     std::unique_ptr<reina_txlog, void (*)(reina_txlog *)> l(new reina_txlog(), free_txlog);   // (freed by a failing return)
     l->e0 = members[0], l->g = g, l->members = members, l->d_refs = d_refs;
     const char *form = std::getenv("REINA_TXLOG_FORM");
@@ -273,22 +265,12 @@ static int txlog_after_day(attachment *a, const reina_day_t &d, hipStream_t s) {
 
 static int txlog_report(reina_txlog *l, const uint8_t *age_group, uint32_t n_groups, uint32_t n_days, uint64_t *dev_report, hipStream_t s) {
     TxlArgs a;
-    if (int rc = age_group_args(l->e0, age_group, n_groups, REINA_TXLOG_MAX_GROUPS, "txlog report", &a.p)) return rc;
-    a.n_days = n_days;
-    if (n_days < 1u || n_days > REINA_MAX_DAYS) {
-        g_last_error = "txlog report: n_days must be in [1, REINA_MAX_DAYS]";
-        return REINA_E_INVALID;
-    }
-    if (!dev_report || (reinterpret_cast<uintptr_t>(dev_report) & 15u)) {
-        g_last_error = "txlog report: the report must be a 16-byte aligned device buffer";
-        return REINA_E_INVALID;
-    }
+    uint32_t grid;
+    if (int rc = day_report(l, "txlog report", REINA_TXLOG_MAX_GROUPS, [](uint32_t d) -> size_t { return REINA_TXLOG_REPORT_WORDS(d); }, age_group, n_groups, n_days,
+                            dev_report, s, &a, &grid))
+        return rc;
     const uint32_t K = (uint32_t)l->members.size();
-    const size_t block = REINA_TXLOG_REPORT_WORDS(n_days) * 8u;
-    HIP_CHECK(hipMemsetAsync(dev_report, 0, block * K, s));
-    HIP_CHECK(hipMemset2DAsync(dev_report + REINA_TXLOG_SCALARS + REINA_TXLOG_S_FIRST_DAY, block, 0xFF, 8u, K, s));
-    // (four workgroups a compute unit: each flushes its LDS tables once)
-    const uint32_t grid = member_grid(l->e0->n_cus, K, (a.p.n_agents + TXL_TILE - 1u) / TXL_TILE, 4u);
+    HIP_CHECK(hipMemset2DAsync(dev_report + REINA_TXLOG_SCALARS + REINA_TXLOG_S_FIRST_DAY, REINA_TXLOG_REPORT_WORDS(n_days) * 8u, 0xFF, 8u, K, s));
     launch_members(k_txlog_report, l->g, grid, K, TXL_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, dev_report, a);
     return REINA_OK;
 }
@@ -345,26 +327,12 @@ int reina_group_txlog_report(reina_txlog_t *log, const uint8_t *age_group, uint3
 
 int reina_txlog_read(reina_txlog_t *log, uint32_t member, uint32_t *out_host, void *stream) {
     if (!log || !out_host) return REINA_E_INVALID;
-    if (member >= log->members.size()) {
-        g_last_error = "txlog: member out of range";
-        return REINA_E_INVALID;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    HIP_CHECK(hipMemcpyAsync(out_host, log->d_log + (size_t)member * log->stride, sizeof(uint32_t) * log->e0->cfg.n_agents, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return REINA_OK;
+    return member_copy(log, log->d_log, log->stride, sizeof(uint32_t), member, out_host, true, "txlog", (hipStream_t)stream);
 }
 
 int reina_txlog_write(reina_txlog_t *log, uint32_t member, const uint32_t *in_host, void *stream) {
     if (!log || !in_host) return REINA_E_INVALID;
-    if (member >= log->members.size()) {
-        g_last_error = "txlog: member out of range";
-        return REINA_E_INVALID;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    HIP_CHECK(hipMemcpyAsync(log->d_log + (size_t)member * log->stride, in_host, sizeof(uint32_t) * log->e0->cfg.n_agents, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return REINA_OK;
+    return member_copy(log, log->d_log, log->stride, sizeof(uint32_t), member, const_cast<uint32_t *>(in_host), false, "txlog", (hipStream_t)stream);
 }
 
 }  // extern "C"

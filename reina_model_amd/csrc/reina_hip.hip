@@ -155,34 +155,17 @@ static void resolve_profile(reina_engine *e) {
 // frees what reina_create / reina_group_create had acquired when a later step fails
 static void free_engine(reina_engine *e) {
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
-    for (size_t k = 0; k < e->stage.size(); k++) {
-        (void)hipEventSynchronize(e->stage_ev[k]);
-        (void)hipEventDestroy(e->stage_ev[k]);
-        (void)hipHostFree(e->stage[k]);
-    }
+    e->stage.free();
+    e->days_stage.free();
     if (e->d_params) (void)hipFree(e->d_params);
     if (e->d_tables) (void)hipFree(e->d_tables);
     if (e->d_ref) (void)hipFree(e->d_ref);
     if (e->d_bar) (void)hipFree(e->d_bar);
     if (e->d_days) (void)hipFree(e->d_days);
     if (e->d_snap) (void)hipFree(e->d_snap);
-    for (size_t k = 0; k < e->days_stage.size(); k++) {
-        (void)hipEventSynchronize(e->days_stage_ev[k]);
-        (void)hipEventDestroy(e->days_stage_ev[k]);
-        (void)hipHostFree(e->days_stage[k]);
-    }
     if (e->counted_live) g_live_engines--;
     delete e;
 }
-#define HIP_CHECK_OR(x, cleanup)                                                             \
-    do {                                                                                     \
-        hipError_t _e = (x);                                                                 \
-        if (_e != hipSuccess) {                                                              \
-            g_last_error = std::string(#x) + ": " + hipGetErrorString(_e);                   \
-            cleanup;                                                                         \
-            return REINA_E_HIP;                                                              \
-        }                                                                                    \
-    } while (0)
 
 // One row of contact-count thresholds + its guide table (reina_contacts.h: 105 erfc + log in double, 4 us a row, 80 us for the
 // 20 distinct rows of a table -- host time that a short run cannot hide behind the GPU: the 20-day window of the round
@@ -279,21 +262,14 @@ const char *reina_last_error(void) { return g_last_error.c_str(); }
 int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, reina_engine_t **out) {
     if (!cfg || !disease || !out) return REINA_E_INVALID;
     if (cfg->nr_ages == 0 || cfg->nr_ages > REINA_MAX_AGES || cfg->nr_variants == 0 ||
-        cfg->nr_variants > REINA_MAX_VARIANTS) {
-        g_last_error = "nr_ages / nr_variants out of range";
-        return REINA_E_INVALID;
-    }
+        cfg->nr_variants > REINA_MAX_VARIANTS)
+        return refuse("nr_ages / nr_variants out of range");
     int ndev = 0;
     HIP_CHECK(hipGetDeviceCount(&ndev));
-    if (ndev == 0) {
-        g_last_error = "no HIP device";
-        return REINA_E_HIP;
-    }
+    if (ndev == 0) return refuse("no HIP device", REINA_E_HIP);
     for (uint32_t a = 0; a < cfg->nr_ages; a++)
-        if (cfg->age_start[a] < 0 || cfg->age_start[a] > cfg->age_start[a + 1] || (uint32_t)cfg->age_start[a + 1] > cfg->n_agents) {
-            g_last_error = "age_start must be non-decreasing and end at n_agents";
-            return REINA_E_INVALID;
-        }
+        if (cfg->age_start[a] < 0 || cfg->age_start[a] > cfg->age_start[a + 1] || (uint32_t)cfg->age_start[a + 1] > cfg->n_agents)
+            return refuse("age_start must be non-decreasing and end at n_agents");
     reina_engine *e = new reina_engine();
     e->cfg = *cfg;
     {   // compute units of the current device: grids of one-workgroup-per-CU kernels are sized to it
@@ -344,9 +320,8 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
     e->h_params.nr_variants = cfg->nr_variants;
     e->cfg.n_shards = cfg->n_shards ? cfg->n_shards : 1;
     if (e->cfg.n_shards > REINA_MAX_SHARDS || e->cfg.shard_rank >= e->cfg.n_shards) {
-        g_last_error = "n_shards / shard_rank out of range";
         delete e;
-        return REINA_E_INVALID;
+        return refuse("n_shards / shard_rank out of range");
     }
     const uint64_t shard_seed = rp_shard_seed(cfg->seed, e->cfg.shard_rank);
     e->h_params.k0 = (uint32_t)shard_seed;
@@ -361,9 +336,8 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
     e->h_params.shard_rank = e->cfg.shard_rank;
     e->h_params.mirror_slots = cfg->mirror_slots ? cfg->mirror_slots : 64;
     if (e->h_params.mirror_slots & (e->h_params.mirror_slots - 1)) {
-        g_last_error = "mirror_slots must be a power of two";
         delete e;
-        return REINA_E_INVALID;
+        return refuse("mirror_slots must be a power of two");
     }
     for (uint32_t v = 0; v < cfg->nr_variants; v++) {
         float m = 0.0f;
@@ -376,9 +350,8 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
     e->h_params.gid_mask = 0xFFFFFFFFu;
     if (e->exact) {
         if (!cfg->shard_age_start || cfg->xchg_cap == 0 || cfg->pool_cap == 0 || cfg->n_agents > RP_GID_INDEX_MASK) {
-            g_last_error = "exact attribution needs shard_age_start, xchg_cap > 0, pool_cap > 0 and fewer than 2^27 agents per shard";
             delete e;
-            return REINA_E_INVALID;
+            return refuse("exact attribution needs shard_age_start, xchg_cap > 0, pool_cap > 0 and fewer than 2^27 agents per shard");
         }
         e->h_params.exact = 1u;
         e->h_params.gid_base = e->cfg.shard_rank << RP_GID_SHIFT;
@@ -408,9 +381,8 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
     e->h_params.hosp_ranges = cfg->hosp_ranges ? cfg->hosp_ranges : REINA_HOSP_RANGES(cfg->n_agents);
     e->h_params.xchg_stride = (uint32_t)REINA_XCHG_SEG_WORDS(e->h_params.xchg_cap, e->h_params.hosp_ranges);   // (exact attribution: a segment = count + records + trailer)
     if (e->h_params.hosp_ranges < 16 || e->h_params.hosp_ranges > REINA_HOSP_MAX_RANGES || (e->h_params.hosp_ranges & (e->h_params.hosp_ranges - 1))) {
-        g_last_error = "hosp_ranges must be a power of two in [16, REINA_HOSP_MAX_RANGES]";
         delete e;
-        return REINA_E_INVALID;
+        return refuse("hosp_ranges must be a power of two in [16, REINA_HOSP_MAX_RANGES]");
     }
     e->h_params.hosp_range_bits = 0;
     while ((1u << e->h_params.hosp_range_bits) < e->h_params.hosp_ranges) e->h_params.hosp_range_bits++;
@@ -419,10 +391,9 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
     e->h_params.hosp_parallel = (cfg->n_agents > REINA_HOSP_SMALL_AGENTS || e->cfg.n_shards > 1) ? 1u : 0u;
     e->exchange_words = (uint32_t)REINA_EXCHANGE_WORDS(e->cfg.n_shards, e->h_params.hosp_ranges);
     if (e->h_params.hosp_parallel && e->h_params.hosp_bucket_cap > REINA_HOSP_MAX_BUCKET_KEYS) {
-        g_last_error = "max_hosp_events too large for this population: a bucket of the event walk holds at most 4096 keys "
-                       "(pass at most REINA_HOSP_MAX_EVENTS_FOR(n_agents), include/reina_hip.h)";
         delete e;
-        return REINA_E_INVALID;
+        return refuse("max_hosp_events too large for this population: a bucket of the event walk holds at most 4096 keys "
+                      "(pass at most REINA_HOSP_MAX_EVENTS_FOR(n_agents), include/reina_hip.h)");
     }
     HIP_CHECK_OR(hipMalloc(&e->d_params, sizeof(DevParams)), free_engine(e));
     HIP_CHECK_OR(hipMalloc(&e->d_tables, sizeof(Tables)), free_engine(e));
@@ -455,10 +426,10 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
             hipFuncAttributes fa;
             HIP_CHECK_OR(hipFuncGetAttributes(&fa, k), free_engine(e));
             if (fa.numRegs != 128 || fa.localSizeBytes != 0) {
-                g_last_error = "k_day was built with " + std::to_string(fa.numRegs) + " VGPRs / " + std::to_string(fa.localSizeBytes) +
-                               " bytes of scratch: it names v104..v127 by hand and needs 128 / 0 (rebuild with the ROCm release the sources were written for)";
                 free_engine(e);
-                return REINA_E_HIP;
+                return refuse("k_day was built with " + std::to_string(fa.numRegs) + " VGPRs / " + std::to_string(fa.localSizeBytes) +
+                                  " bytes of scratch: it names v104..v127 by hand and needs 128 / 0 (rebuild with the ROCm release the sources were written for)",
+                              REINA_E_HIP);
             }
         }
     }
@@ -493,10 +464,7 @@ int reina_bind_buffers(reina_engine_t *e, const reina_buffers_t *b) {
     if (!e || !b) return REINA_E_INVALID;
     const void *const *p = reinterpret_cast<const void *const *>(b);
     for (size_t k = 0; k < sizeof(reina_buffers_t) / sizeof(void *); k++)
-        if (!p[k]) {
-            g_last_error = "null buffer pointer";
-            return REINA_E_INVALID;
-        }
+        if (!p[k]) return refuse("null buffer pointer");
     e->buf = *b;
     e->bound = true;
     MemberRef r;
@@ -529,8 +497,7 @@ int reina_set_initial_state(reina_engine_t *e, const reina_initial_state_t *ic, 
         // (the reference raises AssertionError out of Context.__init__: an agent bound for ICU is refused a bed and
         // Population.transfer_to_icu asserts state == HOSPITALIZED, main.pyx:1495 -> :350 -> :1603; a shard cannot tell --
         // its own share of the beds may be 0 while the population has some -- and leaves the check to its caller)
-        g_last_error = "initial population condition: people in ICU but a hospital without beds (the reference refuses it)";
-        return REINA_E_INVALID;
+        return refuse("initial population condition: people in ICU but a hospital without beds (the reference refuses it)");
     }
     hipLaunchKernelGGL(k_initial_state, dim3(1, 1), dim3(PRO_THREADS), 0, (hipStream_t)stream, e->d_ref, *ic);
     HIP_CHECK(hipGetLastError());
@@ -542,24 +509,15 @@ int reina_set_initial_state(reina_engine_t *e, const reina_initial_state_t *ic, 
 // the engine's own mirrors, a policy's bank (k_policy.inc) into its entries'.
 static int derive_contact_tables(const reina_engine_t *e, const reina_contact_tables_t *t, DevParams &hp, Tables &ht) {
     const uint32_t A = e->cfg.nr_ages;
-    if (t->n_ranges > REINA_MAX_RANGES) {
-        g_last_error = "more than REINA_MAX_RANGES contact ranges";
-        return REINA_E_INVALID;
-    }
+    if (t->n_ranges > REINA_MAX_RANGES) return refuse("more than REINA_MAX_RANGES contact ranges");
     for (uint32_t a = 0; a < A; a++)
-        if (t->count[a] < 0 || t->count[a] > REINA_MAX_ENTRIES) {
-            g_last_error = "contact entries per age must be in [0, REINA_MAX_ENTRIES]";
-            return REINA_E_INVALID;
-        }
+        if (t->count[a] < 0 || t->count[a] > REINA_MAX_ENTRIES) return refuse("contact entries per age must be in [0, REINA_MAX_ENTRIES]");
     for (uint32_t a = 0; a < A; a++)
         if (t->count[a] == 0 && t->nr_contacts_by_age[a] > 0.0f) {   // (k_day would read entry 0 of an empty row)
-            g_last_error = "age " + std::to_string(a) + " has contacts (nr_contacts_by_age > 0) but no contact entries (count == 0)";
-            return REINA_E_INVALID;
+            return refuse("age " + std::to_string(a) + " has contacts (nr_contacts_by_age > 0) but no contact entries (count == 0)");
         }
-    if (e->cfg.n_shards > 1 && t->n_ranges >= REINA_MAX_RANGES) {
-        g_last_error = "a sharded engine takes at most REINA_MAX_RANGES - 1 contact ranges (the last range's pressure words carry free capacity)";
-        return REINA_E_INVALID;
-    }
+    if (e->cfg.n_shards > 1 && t->n_ranges >= REINA_MAX_RANGES)
+        return refuse("a sharded engine takes at most REINA_MAX_RANGES - 1 contact ranges (the last range's pressure words carry free capacity)");
     std::memcpy(hp.nrc, t->nr_contacts_by_age, sizeof(float) * A);
     std::memcpy(hp.tcount, t->count, sizeof(int32_t) * A);
     std::memcpy(hp.mask_p, t->mask_p, sizeof(float) * A * 8);
@@ -647,26 +605,10 @@ static int derive_contact_tables(const reina_engine_t *e, const reina_contact_ta
 
 // the pinned-staging, kernel-reads-host route of an upload: `hp` whole and the used rows of `ht` into d_params / d_tables
 static int stage_upload(reina_engine_t *e, const DevParams &hp, const Tables &ht, DevParams *d_params, Tables *d_tables, hipStream_t s) {
-    size_t slot = e->stage.size();
-    for (size_t k = 0; k < e->stage.size(); k++)
-        if (hipEventQuery(e->stage_ev[k]) == hipSuccess) {
-            slot = k;
-            break;
-        }
-    if (slot == e->stage.size()) {
-        if (e->stage.size() < reina_engine::MAX_STAGES) {
-            reina_engine::Stage *st = nullptr;
-            hipEvent_t ev;
-            HIP_CHECK(hipHostMalloc((void **)&st, sizeof(reina_engine::Stage), hipHostMallocDefault));
-            HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            e->stage.push_back(st);
-            e->stage_ev.push_back(ev);
-        } else {
-            slot = 0;
-            HIP_CHECK(hipEventSynchronize(e->stage_ev[0]));
-        }
-    }
-    std::memcpy(&e->stage[slot]->p, &hp, sizeof(DevParams));
+    void *block = nullptr, *dsrc = nullptr;
+    if (int rc = e->stage.acquire(sizeof(reina_engine::Stage), reina_engine::MAX_STAGES, &block, &dsrc)) return rc;
+    reina_engine::Stage *st = static_cast<reina_engine::Stage *>(block);
+    std::memcpy(&st->p, &hp, sizeof(DevParams));
     UploadSegs segs;
     {
         const Tables &T = ht;
@@ -683,7 +625,7 @@ static int stage_upload(reina_engine_t *e, const DevParams &hp, const Tables &ht
         };
         segs.n = 8;
         for (int q = 0; q < 8; q++) {
-            std::memcpy(reinterpret_cast<char *>(&e->stage[slot]->t) + seg[q][0], reinterpret_cast<const char *>(&T) + seg[q][0], seg[q][1]);
+            std::memcpy(reinterpret_cast<char *>(&st->t) + seg[q][0], reinterpret_cast<const char *>(&T) + seg[q][0], seg[q][1]);
             segs.off[q] = (uint32_t)(seg[q][0] / 4);
             segs.words[q] = (uint32_t)(seg[q][1] / 4);
         }
@@ -691,8 +633,6 @@ static int stage_upload(reina_engine_t *e, const DevParams &hp, const Tables &ht
     // The transfer is a KERNEL that reads the pinned host slot directly (zero-copy): an ordinary
     // dispatch in the day stream.  hipMemcpyAsync of the 98 KB table was measured to block the host
     // for 7-8 ms once per run when >1000 dispatches were queued ahead of it (ROCm 7.2).
-    void *dsrc = nullptr;
-    HIP_CHECK(hipHostGetDevicePointer(&dsrc, e->stage[slot], 0));
     static_assert(sizeof(DevParams) % 4 == 0 && sizeof(Tables) % 4 == 0 && offsetof(reina_engine::Stage, t) % 4 == 0 &&
                   offsetof(Tables, meta) % 4 == 0 && offsetof(Tables, guide) % 4 == 0 && offsetof(Tables, grp) % 4 == 0 && offsetof(Tables, rcount) % 4 == 0 &&
                   offsetof(Tables, cthr) % 4 == 0 && offsetof(Tables, cguide) % 4 == 0 && offsetof(Tables, crow_of_age) % 4 == 0, "word copies");
@@ -700,8 +640,7 @@ static int stage_upload(reina_engine_t *e, const DevParams &hp, const Tables &ht
     hipLaunchKernelGGL(k_upload, dim3(64), dim3(256), 0, s, reinterpret_cast<uint32_t *>(d_params), src_w,
                        (uint32_t)(sizeof(DevParams) / 4), reinterpret_cast<uint32_t *>(d_tables),
                        src_w + offsetof(reina_engine::Stage, t) / 4, segs);
-    HIP_CHECK(hipEventRecord(e->stage_ev[slot], s));
-    return REINA_OK;
+    return e->stage.release_behind(s);
 }
 
 int reina_upload_contact_tables(reina_engine_t *e, const reina_contact_tables_t *t, void *stream) {
@@ -738,13 +677,9 @@ static int day_geometry(reina_engine_t *e, uint32_t K, const reina_day_t &dp, Da
     if (dp.day >= REINA_MAX_DAYS) {
         // claim / mirror keys carry the day in 12 bits (rp_order_key) and claim[] is never cleared: from day
         // 4096 on, stale claims would beat today's
-        g_last_error = "day >= REINA_MAX_DAYS (4096): the winner-selection keys carry the day in 12 bits";
-        return REINA_E_INVALID;
+        return refuse("day >= REINA_MAX_DAYS (4096): the winner-selection keys carry the day in 12 bits");
     }
-    if (dp.n_import_batches > REINA_MAX_IMPORT_BATCHES || dp.n_vaccinations > REINA_MAX_VACCINATIONS) {
-        g_last_error = "n_import_batches / n_vaccinations out of range";
-        return REINA_E_INVALID;
-    }
+    if (dp.n_import_batches > REINA_MAX_IMPORT_BATCHES || dp.n_vaccinations > REINA_MAX_VACCINATIONS) return refuse("n_import_batches / n_vaccinations out of range");
     if (dp.testing_mode != RT_NO_TESTING) e->testing_ever = true;
     uint32_t n_pre = 0, n_post = 0;
     for (uint32_t b = 0; b < dp.n_import_batches; b++)
@@ -1003,34 +938,15 @@ static bool small_day_record(reina_engine_t *e, const reina_day_t &dp, SmallDayR
 }
 static int launch_small_days(reina_engine_t *e, const SmallDayRec *recs, uint32_t n, hipStream_t s) {
     // the records travel like the tables: a pinned slot the host fills, a copy kernel in the day stream (reina_upload_contact_tables)
-    size_t slot = e->days_stage.size();
-    for (size_t k = 0; k < e->days_stage.size(); k++)
-        if (hipEventQuery(e->days_stage_ev[k]) == hipSuccess) {
-            slot = k;
-            break;
-        }
-    if (slot == e->days_stage.size()) {
-        if (e->days_stage.size() < reina_engine::MAX_STAGES) {
-            SmallDayRec *st = nullptr;
-            hipEvent_t ev;
-            HIP_CHECK(hipHostMalloc((void **)&st, sizeof(SmallDayRec) * SMALL_MAX_DAYS, hipHostMallocDefault));
-            HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            e->days_stage.push_back(st);
-            e->days_stage_ev.push_back(ev);
-        } else {
-            slot = 0;
-            HIP_CHECK(hipEventSynchronize(e->days_stage_ev[0]));
-        }
-    }
-    std::memcpy(e->days_stage[slot], recs, sizeof(SmallDayRec) * n);
-    void *dsrc = nullptr;
-    HIP_CHECK(hipHostGetDevicePointer(&dsrc, e->days_stage[slot], 0));
+    void *block = nullptr, *dsrc = nullptr;
+    if (int rc = e->days_stage.acquire(sizeof(SmallDayRec) * SMALL_MAX_DAYS, reina_engine::MAX_STAGES, &block, &dsrc)) return rc;
+    std::memcpy(block, recs, sizeof(SmallDayRec) * n);
     UploadSegs none;
     std::memset(&none, 0, sizeof(none));
     const uint32_t words = (uint32_t)(sizeof(SmallDayRec) * n / 4);
     hipLaunchKernelGGL(k_upload, dim3(words / 256u + 1u < 64u ? words / 256u + 1u : 64u), dim3(256), 0, s, reinterpret_cast<uint32_t *>(e->d_days),
                        reinterpret_cast<const uint32_t *>(dsrc), words, (uint32_t *)nullptr, (const uint32_t *)nullptr, none);
-    HIP_CHECK(hipEventRecord(e->days_stage_ev[slot], s));
+    if (int rc = e->days_stage.release_behind(s)) return rc;
     const uint32_t N = e->cfg.n_agents, W = e->small_wgs;
     SmallGeom g;
     std::memset(&g, 0, sizeof(g));
@@ -1122,28 +1038,21 @@ int reina_step_phase(reina_engine_t *e, const reina_day_t *day, int phase, void 
     case REINA_PH_FEEDBACK:
         return launch_day_feedback(e, e->d_ref, 1, *day, s);
     }
-    g_last_error = "phase out of range";
-    return REINA_E_INVALID;
+    return refuse("phase out of range");
 }
 
 // the two halves of a day around its one all-reduce (a population without exact attribution)
 int reina_step_day_begin(reina_engine_t *e, const reina_day_t *day, void *stream) {
     if (!e || !day) return REINA_E_INVALID;
     if (!e->bound) return REINA_E_NOT_BOUND;
-    if (e->exact) {
-        g_last_error = "exact attribution: a day has more than one exchange -- step it by reina_step_phase (or reina_step_day with reina_set_alltoall)";
-        return REINA_E_INVALID;
-    }
+    if (e->exact) return refuse("exact attribution: a day has more than one exchange -- step it by reina_step_phase (or reina_step_day with reina_set_alltoall)");
     return launch_day_begin(e, e->d_ref, 1, *day, 0, (hipStream_t)stream);
 }
 
 int reina_step_day_end(reina_engine_t *e, const reina_day_t *day, void *stream) {
     if (!e || !day) return REINA_E_INVALID;
     if (!e->bound) return REINA_E_NOT_BOUND;
-    if (e->exact) {
-        g_last_error = "exact attribution: a day has more than one exchange -- step it by reina_step_phase (or reina_step_day with reina_set_alltoall)";
-        return REINA_E_INVALID;
-    }
+    if (e->exact) return refuse("exact attribution: a day has more than one exchange -- step it by reina_step_phase (or reina_step_day with reina_set_alltoall)");
     return launch_day_end(e, e->d_ref, 1, *day, (hipStream_t)stream);
 }
 
@@ -1172,21 +1081,13 @@ int reina_step_day(reina_engine_t *e, const reina_day_t *day, void *stream) {
                            take_event_pair(e, &ev_a, &ev_b) && hipEventRecord(e->ev_pool[ev_a], (hipStream_t)stream) == hipSuccess;
         if ((need & REINA_X_ALLREDUCE) && e->coll_fn) {
             const int r = e->coll_fn(e->buf.pressure, e->buf.pressure, e->exchange_words, 2 /* ncclInt32 */, 0 /* ncclSum */, e->coll_comm, stream);
-            if (r != 0) {
-                g_last_error = "collective failed with code " + std::to_string(r);
-                return REINA_E_HIP;
-            }
+            if (r != 0) return refuse("collective failed with code " + std::to_string(r), REINA_E_HIP);
         }
         if (need & REINA_X_ALLTOALL) {
-            if (!e->a2a_fn) {
-                g_last_error = "exact attribution: no all-to-all set (reina_set_alltoall) -- step the day by reina_step_phase and exchange buffers.xsend / xrecv yourself";
-                return REINA_E_NOT_BOUND;
-            }
+            if (!e->a2a_fn)
+                return refuse("exact attribution: no all-to-all set (reina_set_alltoall) -- step the day by reina_step_phase and exchange buffers.xsend / xrecv yourself", REINA_E_NOT_BOUND);
             const int r = e->a2a_fn(e->buf.xsend, e->buf.xrecv, (size_t)e->h_params.xchg_stride, 4 /* ncclInt64 */, e->a2a_comm, stream);
-            if (r != 0) {
-                g_last_error = "all-to-all failed with code " + std::to_string(r);
-                return REINA_E_HIP;
-            }
+            if (r != 0) return refuse("all-to-all failed with code " + std::to_string(r), REINA_E_HIP);
         }
         if (timed && hipEventRecord(e->ev_pool[ev_b], (hipStream_t)stream) == hipSuccess) e->kpairs[REINA_PK_COLLECTIVE].emplace_back(ev_a, ev_b);
     }
@@ -1226,10 +1127,8 @@ int reina_group_create(reina_engine_t **engines, uint32_t n, reina_group_t **out
         if (!m || !m->bound) return REINA_E_NOT_BOUND;
         if (m->cfg.n_agents != engines[0]->cfg.n_agents || m->cfg.nr_ages != engines[0]->cfg.nr_ages ||
             m->cfg.nr_variants != engines[0]->cfg.nr_variants || m->cfg.n_shards != 1 ||
-            std::memcmp(m->cfg.age_start, engines[0]->cfg.age_start, sizeof(m->cfg.age_start)) != 0) {
-            g_last_error = "group members must be unsharded engines of the same population";
-            return REINA_E_INVALID;
-        }
+            std::memcmp(m->cfg.age_start, engines[0]->cfg.age_start, sizeof(m->cfg.age_start)) != 0)
+            return refuse("group members must be unsharded engines of the same population");
     }
     reina_group *g = new reina_group();
     g->members.assign(engines, engines + n);

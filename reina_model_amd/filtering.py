@@ -150,33 +150,29 @@ def clone_group(group, pairs, log=None):
     (reina_group_txlog_clone: the log's launch ahead of the state's)."""
     engines = group.engines
     e0 = engines[0]
-    if log is not None:
-        from . import reports as _rep
-        f = _rep.entry_points(e0, 'filter_log_f', 'logged-clone', 'reina_filter_log.h')
-        if getattr(log, 'group', None) is not group:
-            raise ValueError('clone: `log` is not the transmission log of this group')
-        flat = [int(x) for pr in pairs for x in pr]
-        if len(flat) % 2:
-            raise ValueError('clone: pairs are (dst, src)')
-        arr = (ctypes.c_uint32 * max(len(flat), 1))(*[x & 0xFFFFFFFF for x in flat])
-        _eng.mark_stale(engines)
-        e0._check(f['group_txlog_clone'](log._h, arr, len(flat) // 2, e0.alloc.stream()), 'group_txlog_clone')
-        return
-    if not _eng.is_device(e0):
+    if log is None and not _eng.is_device(e0):
         p = check_pairs(pairs, len(engines))
         mq = min(e.config.max_queue for e in engines)
         for d, s in p:
             clone_state(_host_arrays(engines[d]), _host_arrays(engines[s]), e0.config.n_agents, mq)
         return
-    f = getattr(e0, 'filter_f', None)
-    if f is None:
-        raise _eng.EngineError('the engine library has no particle-filter entry points (include/reina_filter.h)')
+    if log is not None:
+        from . import reports as _rep
+        f = _rep.entry_points(e0, 'filter_log_f', 'logged-clone', 'reina_filter_log.h')
+        if getattr(log, 'group', None) is not group:
+            raise ValueError('clone: `log` is not the transmission log of this group')
+        name, owner = 'group_txlog_clone', log
+    else:
+        f = getattr(e0, 'filter_f', None)
+        if f is None:
+            raise _eng.EngineError('the engine library has no particle-filter entry points (include/reina_filter.h)')
+        name, owner = 'group_clone', group
     flat = [int(x) for pr in pairs for x in pr]
     if len(flat) % 2:
         raise ValueError('clone: pairs are (dst, src)')
     arr = (ctypes.c_uint32 * max(len(flat), 1))(*[x & 0xFFFFFFFF for x in flat])
     _eng.mark_stale(engines)
-    e0._check(f['group_clone'](group._h, arr, len(flat) // 2, e0.alloc.stream()), 'group_clone')
+    e0._check(f[name](owner._h, arr, len(flat) // 2, e0.alloc.stream()), name)
 
 
 # ------------------------------------------------------------------------------------------------ observation model
