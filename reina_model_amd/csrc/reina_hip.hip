@@ -1360,6 +1360,9 @@ int reina_profile_read(reina_engine_t *e, double *scan_ms_total, uint64_t *scan_
 // the clinical course log attached to a transmission log (include/reina_course.h): kernels and entry points
 #include "k_course.inc"
 
+// the vaccination report taken of a transmission log (include/reina_vaccination.h): kernel and entry point
+#include "k_vaccination.inc"
+
 // the clone of a logged group: the particle filter carries both logs (include/reina_filter_log.h): kernel and entry point
 #include "k_filter_log.inc"
 

@@ -425,3 +425,17 @@ def course_reports(contexts, age_groups=None, n_days=None):
     if glog is not None and glog.course is not None and all(c.course_log.device is glog.course for c in contexts):
         return _crs.report_group(glog.course, contexts, age_groups, n_days)
     return [c.course_log.report(age_groups, n_days) for c in contexts]
+
+
+def vaccination_reports(contexts, age_groups=None, n_days=None):
+    """vaccination.VaccinationReport of every context, between the same two days.  The members of a logged group
+    (run_group_plan(..., txlog=True)) are reported by ONE launch (reina_vacc_report); contexts that keep logs of their own, and
+    engine libraries without the entry points, one by one."""
+    from . import vaccination as _vac
+    contexts = list(contexts)
+    if any(c.transmission_log is None for c in contexts):
+        raise ValueError('vaccination_reports: a context keeps no transmission log')
+    glog = _logged_group(contexts)
+    if glog is not None and getattr(glog.engine, 'vacc_f', None) is not None:
+        return _vac.report_group(glog, contexts, age_groups, n_days)
+    return [c.transmission_log.vaccination_report(age_groups, n_days) for c in contexts]

@@ -490,6 +490,13 @@ class FilterResult:
         self._logged('course_reports', course=True)
         return ensemble.course_reports(self.contexts, age_groups, n_days)
 
+    def vaccination_reports(self, age_groups=None, n_days=None):
+        """vaccination.VaccinationReport of every final particle by one launch (ensemble.vaccination_reports): a clone carries
+        the cold record, so a particle's days of vaccination are those of its whole ancestral path, like its log"""
+        from . import ensemble
+        self._logged('vaccination_reports')
+        return ensemble.vaccination_reports(self.contexts, age_groups, n_days)
+
     def _band_frame(self, values, q, index, means=()):
         import pandas as pd
         q = [float(x) for x in np.atleast_1d(q)]

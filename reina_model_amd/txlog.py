@@ -419,6 +419,14 @@ class TransmissionLog:
         from . import lineage as _lin
         return _lin.report_log(self, period, n_periods, age_groups)
 
+    def vaccination_report(self, age_groups=None, n_days=None):
+        """vaccination.VaccinationReport of the days [0, n_days) (default: the days run so far): coverage by date and age group,
+        infections by status at infection (unvaccinated, recent, protected), the time from the dose to a breakthrough, and the
+        protection realised against severe disease and death.  On the device when the library has the entry points and the
+        log is there, vaccination.report_numpy on host copies otherwise.  Reads the engine's state and the log only."""
+        from . import vaccination as _vac
+        return _vac.report_log(self, age_groups, n_days)
+
     def line_list(self):
         """One row per infected agent (a pandas DataFrame, built on the host from the hot words, the cold records and the log):
         agent, age, infector (-1: an import or the initial condition), infector_age (-1 without one), infection_day and

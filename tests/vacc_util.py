@@ -1,0 +1,216 @@
+"""Test-side helpers of the vaccination report (reina_model_amd/vaccination.py): synthetic states with vaccination days and log
+words of every combination, a plain per-agent walker that counts every field of a report directly, the scenario of the
+simulated runs, and writing a synthetic state into an engine.
+
+A synthetic state is NOT one a simulation could reach; it only ever goes through a report.  Never step a day on one."""
+import bisect
+from datetime import date, timedelta
+
+import numpy as np
+
+import tx_util
+import txlog_util
+from filter_util import small_scenario
+from reina_model_amd import engine as eng
+from reina_model_amd import txlog as txl
+from reina_model_amd import vaccination as vac
+
+N_DAYS = txlog_util.N_DAYS         # the synthetic reports' n_days: some of their known days lie beyond
+VACCINATED, DETECTED = 0x2000, 0x40
+START = date(2020, 2, 18)          # VARIABLE_DEFAULTS' start_date
+
+
+def day_date(day):
+    return (START + timedelta(days=int(day))).isoformat()
+
+
+def vaccination_scenario(n=20000, first=7000, second=3500, day=10):
+    """small_scenario() with a programme of `first` doses a week for the ages 30..100 from day `day` and a later one of
+    `second` a week on an overlapping window, the ages 10..50, from day `day` + 40"""
+    v, ages = small_scenario(n)
+    v['interventions'] = list(v['interventions']) + [['vaccinate', day_date(day), first, 30, 100], ['vaccinate', day_date(day + 40), second, 10, 50]]
+    return v, ages
+
+
+def mass_programme(v, weekly=350000, day=10):
+    """a scenario's variables with one programme for everybody from 16 up added (HUS: a fifth of the population a week)"""
+    v['interventions'] = list(v['interventions']) + [['vaccinate', day_date(day), weekly, 16, 100]]
+    return v
+
+
+def put_vaccinations(ctx, hot, vacc_day):
+    """write the hot words (they carry the flag VACCINATED) and cold word 5 (vacc_day) of a synthetic state into a Context's
+    engine (numpy or torch tensors); beside tx_util.put_forest, which writes the hot words and cold words 2 and 3"""
+    t = ctx.engine.tensors
+    n = ctx.engine.config.n_agents
+    word = eng.COLD_FIELDS['vacc_day']
+    vd = np.ascontiguousarray(vacc_day, dtype=np.int32).reshape(n, 1)
+    if hasattr(t['hot'], 'copy_'):
+        import torch
+        t['hot'].copy_(torch.from_numpy(np.asarray(hot, dtype=np.uint32).view(np.int32)))
+        t['cold'].view(n, eng.COLD_WORDS)[:, word:word + 1].copy_(torch.from_numpy(vd))
+    else:
+        np.asarray(t['hot']).view(np.uint32)[:] = hot
+        np.asarray(t['cold']).reshape(n, eng.COLD_WORDS)[:, word] = vd[:, 0]
+
+
+def random_vaccinations(n, hot, seed=0, top=400, share=0.5):
+    """(hot with the flag on `share` of ALL agents, vacc_day): valid days in [0, top) mostly, -1 and REINA_MAX_DAYS now and then
+    under the flag; agents without the flag hold -1 or garbage, which a report must not look at"""
+    rng = np.random.default_rng([n, seed, 53])
+    flag = rng.random(n) < share
+    kind = rng.integers(0, 12, size=n)
+    vd = rng.integers(0, top, size=n)
+    vd = np.where(kind == 0, -1, np.where(kind == 1, eng.MAX_DAYS, np.where(kind == 2, eng.MAX_DAYS - 1, vd)))
+    vd = np.where(flag, vd, np.where(kind < 6, -1, rng.integers(-2 ** 31, 2 ** 31, size=n)))
+    hot = np.asarray(hot, dtype=np.uint32) & ~np.uint32(VACCINATED)
+    return (hot | np.where(flag, VACCINATED, 0).astype(np.uint32)).astype(np.uint32), vd.astype(np.int32)
+
+
+def forest_state(n, seed=0):
+    """(hot, infector, n_infected, log, vacc_day): a random tx_util forest with random log words and random vaccinations"""
+    hot, inf, cnt, log = txlog_util.forest_state(n, 'random', seed)
+    hot, vd = random_vaccinations(n, hot, seed)
+    return hot, inf, cnt, log, vd
+
+
+# (t, vd) of the combinations: t - vd below 0, 0, 14, 15, 127, 128; days at and beyond N_DAYS on either side; vd -1 and
+# REINA_MAX_DAYS under the flag, and the last valid day; t NONE and BEFORE
+COMBOS = [(200, 205), (200, 200), (200, 186), (200, 185), (200, 73), (200, 72),
+          (N_DAYS + 50, N_DAYS + 10), (N_DAYS - 1, N_DAYS), (N_DAYS, N_DAYS - 1), (N_DAYS - 1, N_DAYS - 1), (N_DAYS + 20, N_DAYS + 3),
+          (200, -1), (200, eng.MAX_DAYS), (200, eng.MAX_DAYS - 1), (txl.NONE, -1), (txl.BEFORE, eng.MAX_DAYS),
+          (txl.NONE, 100), (txl.BEFORE, 100)]
+
+
+def combos_state():
+    """(hot, infector, n_infected, log, vacc_day): one agent for every flag x state 0..6 x severity 0..4 x COMBOS (the
+    unvaccinated ones hold the same vacc_day words: ignored), RH_DETECTED on every other one, scattered over a population with
+    a few untouched agents"""
+    hot, log, vd = [], [], []
+    k = 0
+    for flag in (0, VACCINATED):
+        for st in range(7):
+            for sev in range(5):
+                for t, d in COMBOS:
+                    hot.append(st | sev << 3 | flag | (DETECTED if k % 2 else 0) | (k % 4) << 8)
+                    log.append(((txl.NONE, 150, txl.BEFORE)[k % 3]) << 16 | t)
+                    vd.append(d)
+                    k += 1
+    n = len(hot) + 9
+    rng = np.random.default_rng(17)
+    where = rng.permutation(n)[:len(hot)]
+    H = np.zeros(n, dtype=np.uint32)
+    L = np.full(n, txl.NONE << 16 | txl.NONE, dtype=np.uint32)
+    V = np.full(n, -1, dtype=np.int32)
+    H[where] = np.array(hot, dtype=np.uint32)
+    L[where] = np.array(log, dtype=np.uint32)
+    V[where] = np.array(vd, dtype=np.int32)
+    return H, np.full(n, -1, dtype=np.int32), np.zeros(n, dtype=np.int32), L, V
+
+
+def walk_report(hot, vacc_day, log, age_start, age_group, n_days):
+    """Every field of a report, counted agent by agent in plain Python from the header's text (independent of report_numpy)"""
+    n = len(hot)
+    hot = [int(x) for x in np.asarray(hot, dtype=np.uint32)]
+    vds = [int(x) for x in np.asarray(vacc_day, dtype=np.int32)]
+    log = [int(x) for x in np.asarray(log, dtype=np.uint32)]
+    starts = [int(x) for x in age_start]
+    nr_ages = len(age_group)
+    age = lambda i: min(max(bisect.bisect_right(starts[:nr_ages + 1], i) - 1, 0), nr_ages - 1)
+    severity = np.zeros((4, 16, 8), dtype=np.uint64)
+    outcome = np.zeros((4, 16, 4), dtype=np.uint64)
+    since = np.zeros((2, 16, 128), dtype=np.uint64)
+    population = np.zeros((16, 3), dtype=np.uint64)
+    vaccinations = np.zeros((n_days, 16), dtype=np.uint64)
+    infections = np.zeros((n_days, 16, 3), dtype=np.uint64)
+    cohort = np.zeros((n_days, 3, 4), dtype=np.uint64)
+    sc = {name: 0 for name in vac.SCALAR_NAMES}
+    for i in range(n):
+        w = hot[i]
+        st, sev = w & 7, (w >> 3) & 7
+        vaccinated, infected = bool(w & VACCINATED), st != 0
+        if not vaccinated and not infected:
+            continue
+        g = age_group[age(i)]
+        vd = vds[i] if vaccinated else None
+        valid = vaccinated and 0 <= vd < eng.MAX_DAYS
+        if vaccinated:
+            sc['vaccinated'] += 1
+            population[g, 0] += 1
+            population[g, 2 if infected else 1] += 1
+            if not valid:
+                sc['bad_vacc_day'] += 1
+            elif vd < n_days:
+                vaccinations[vd, g] += 1
+            else:
+                sc['out_of_range'] += 1
+        if not infected:
+            continue
+        sc['infected'] += 1
+        if vaccinated:
+            sc['vaccinated_infected'] += 1
+        t = log[i] & 0xFFFF
+        known = t not in (txl.NONE, txl.BEFORE)
+        if not vaccinated:
+            status = 0
+        elif not valid or not known:
+            status = 3
+            sc['undetermined'] += 1
+        elif vd > t:
+            status = 0
+            sc['after_infection'] += 1
+        elif t - vd <= 14:
+            status = 1
+        else:
+            status = 2
+        severity[status, g, sev] += 1
+        outcome[status, g, 0] += 1
+        if st >= 5:
+            outcome[status, g, 1] += 1
+        if st == 6:
+            outcome[status, g, 2] += 1
+        if w & DETECTED:
+            outcome[status, g, 3] += 1
+        if status in (1, 2):
+            b = min(t - vd, 127)
+            since[0, g, b] += 1
+            if sev >= 2:
+                since[1, g, b] += 1
+        if status <= 2 and known:
+            if t < n_days:
+                infections[t, g, status] += 1
+                cohort[t, status, 0] += 1
+                if sev >= 2:
+                    cohort[t, status, 1] += 1
+                if st == 6:
+                    cohort[t, status, 2] += 1
+                if st >= 5:
+                    cohort[t, status, 3] += 1
+            else:
+                sc['out_of_range'] += 1
+    w = np.concatenate([severity.ravel(), outcome.ravel(), since.ravel(), population.ravel(),
+                        np.array([sc[name] for name in vac.SCALAR_NAMES] + [0] * (vac.S_NR - len(vac.SCALAR_NAMES)), dtype=np.uint64),
+                        vaccinations.ravel(), infections.ravel(), cohort.ravel()])
+    assert len(w) == vac.report_words(n_days)
+    return w
+
+
+def assert_words(got, want):
+    got, want = np.asarray(got, dtype=np.uint64), np.asarray(want, dtype=np.uint64)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    bad = np.flatnonzero(got != want)
+    assert not len(bad), [(int(k), int(got[k]), int(want[k])) for k in bad[:8]]
+
+
+def host_arrays(ctx):
+    """(hot uint32[N], vacc_day int32[N]) of a Context's engine, host copies"""
+    g = lambda name: (lambda t: np.array(t.cpu().numpy() if hasattr(t, 'cpu') else t))(ctx.engine.tensors[name])
+    n = ctx.engine.config.n_agents
+    return g('hot').view(np.uint32), g('cold').view(np.int32).reshape(n, eng.COLD_WORDS)[:, eng.COLD_FIELDS['vacc_day']].copy()
+
+
+def spec_report(ctx, n_days=None, groups=None, log_words=None):
+    """report_numpy of a Context's read-back state (hot, cold word 5) and its log words"""
+    hot, vd = host_arrays(ctx)
+    log = ctx.transmission_log.words() if log_words is None else log_words
+    return vac.report_numpy(hot, vd, log, ctx.age_start, ctx._tx_groups(groups)[0], max(ctx.day, 1) if n_days is None else n_days)
