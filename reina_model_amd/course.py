@@ -38,7 +38,6 @@ import numpy as np
 from . import engine as _eng
 from . import reports as _rep
 from . import txlog as _txl
-from .reports import _group_table
 from .txlog import BEFORE, NONE, check_n_days
 
 COURSE_VERSION = 1             # include/reina_course.h: REINA_COURSE_VERSION
@@ -283,8 +282,11 @@ class CourseReport(_rep.Report):
 
 # ------------------------------------------------------------------------------------------------ course logs
 
-class DeviceCourse:
+class DeviceCourse(_eng.Handle):
     """The library's course log of a txlog.DeviceLog: of one engine, or of the members of an engine group."""
+    DESTROY = 'course_destroy'
+    group = property(lambda self: self.log.group)       # (with `engines`: what reports.device_take reads of a log on the device)
+    engines = property(lambda self: self.log.engines)
 
     def __init__(self, device_log):
         e = device_log.engine
@@ -296,18 +298,9 @@ class DeviceCourse:
         e._check(f['course_create'](device_log._h, e.alloc.stream(), ctypes.byref(self._h)), 'course_create')
         device_log.course = self
 
-    def close(self):
-        if self._h:
-            self.f['course_destroy'](self._h)
-            self._h = ctypes.c_void_p()
-            if self.log.course is self:
-                self.log.course = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _closing(self):
+        if self.log.course is self:
+            self.log.course = None
 
     def words(self, member=0):
         out = np.zeros(self.engine.config.n_agents, dtype=np.uint64)
@@ -319,11 +312,6 @@ class DeviceCourse:
         if len(w) != self.engine.config.n_agents:
             raise ValueError('a course log has one record per agent')
         self.engine._check(self.f['course_write'](self._h, int(member), w.ctypes.data, self.engine.alloc.stream()), 'course_write')
-
-    def report_words(self, table, n_groups, n_days):
-        """[members, report_words(n_days)] uint64: one launch for all members"""
-        return _rep.device_words(self.engine, self.f, 'course_report', (self._h, table.ctypes.data, int(n_groups), int(n_days)),
-                                 self.members, report_words(n_days), stale=self.log.engines)
 
 
 class CourseLog:
@@ -379,14 +367,7 @@ class CourseLog:
 
     def report(self, age_groups=None, n_days=None):
         """CourseReport of the days [0, n_days) (default: the days run so far)"""
-        ctx = self.ctx
-        if self.device is not None and self.device.log.group is None:
-            return report_group(self.device, [ctx], age_groups, n_days)[0]
-        table, labels = ctx._tx_groups(age_groups)
-        n_days = check_n_days(max(int(ctx.day), 1) if n_days is None else n_days)
-        hot = _rep.host_state(ctx.engine)[0]
-        w = report_numpy(hot, self.log.words(), self.words(), ctx.age_start, table, n_days).words
-        return CourseReport(w, n_days, len(labels), labels, ctx.start_date)
+        return _rep.report_of(COURSE, self, age_groups, n_days)
 
 
 def run_host_driven(ctx, days, record_history=True, on_day=None):
@@ -410,11 +391,13 @@ def run_host_driven(ctx, days, record_history=True, on_day=None):
     return _txl.run_host_driven(ctx, days, record_history, each)
 
 
+COURSE = _rep.Kind(
+    name='course_reports', of='course_log', arguments=_txl.day_arguments, report=CourseReport, words=report_words,
+    numpy=lambda ctx, course, table, params: lambda depth: report_numpy(_rep.host_state(ctx.engine)[0], course.log.words(), course.words(),
+                                                                         ctx.age_start, table, *params).words,
+    names=('course_report', 'course_report'), on=lambda glog: glog.course)
+
+
 def report_group(device_course, contexts, age_groups=None, n_days=None):
     """The reports of every member of a group's course log (or of the one engine of a device course): one launch for all."""
-    c0 = contexts[0]
-    table, labels = c0._tx_groups(age_groups)
-    n_days = check_n_days(max(int(c0.day), 1) if n_days is None else n_days)
-    t8, ng = _group_table(table, c0.nr_ages)
-    w = device_course.report_words(t8, max(ng, len(labels)), n_days)
-    return [CourseReport(r, n_days, len(labels), labels, c.start_date) for r, c in zip(_rep.member_rows(w), contexts)]
+    return _rep.reports_of_device(COURSE, device_course, contexts, age_groups, n_days)

@@ -370,8 +370,31 @@ class TorchAllocator:
         return t.cpu().numpy()
 
 
-class Engine:
+class Handle:
+    """The owner of one library handle (self._h, made by the subclass): close() destroys it once, through the entry point
+    self.f[DESTROY], after _closing() -- what goes with the handle -- and the object closes when it is collected."""
+    DESTROY = None
+    _h = None
+
+    def _closing(self):
+        pass
+
+    def close(self):
+        if self._h:
+            self._closing()
+            self.f[self.DESTROY](self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Engine(Handle):
     """One engine instance = one shard of agents on one device."""
+    DESTROY = 'destroy'
 
     def __init__(self, lib, prefix, allocator, config, disease):
         self.f = bind_abi(lib, prefix)
@@ -434,17 +457,6 @@ class Engine:
         if rc != 0:
             msg = self.f['last_error']()
             raise EngineError('%s failed (%d): %s' % (what, rc, msg.decode() if msg else ''))
-
-    def close(self):
-        if self._h:
-            self.f['destroy'](self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def init_state(self, beds, icu_units):
         self._check(self.f['init_state'](self._h, int(beds), int(icu_units), self.alloc.stream()), 'init_state')
@@ -564,9 +576,10 @@ class Engine:
         return {k: (ms[i], int(cnt[i])) for i, k in enumerate(PROFILE_KINDS)}
 
 
-class EngineGroup:
+class EngineGroup(Handle):
     """K unsharded engines of the same population (different seeds) stepped with one launch per
     phase for all of them (include/reina_hip.h: reina_group_*).  Members stay usable on their own."""
+    DESTROY = 'group_destroy'
 
     def __init__(self, engines):
         self.engines = list(engines)
@@ -576,17 +589,6 @@ class EngineGroup:
         hs = (ctypes.c_void_p * len(self.engines))(*[e._h.value for e in self.engines])
         self._h = ctypes.c_void_p()
         e0._check(self.f['group_create'](hs, len(self.engines), ctypes.byref(self._h)), 'group_create')
-
-    def close(self):
-        if self._h:
-            self.f['group_destroy'](self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def upload_contact_tables(self, nrc, count, threshold, meta, mask_p, ranges):
         t, _keep = Engine._tables_abi(nrc, count, threshold, meta, mask_p, ranges)

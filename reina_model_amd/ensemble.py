@@ -20,7 +20,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import simulation
+from . import course as _crs, lineage as _lin, reports as _rep, simulation, txlog as _txl, vaccination as _vac
 from .dayrun import History, replay_plan
 from .filtering import particle_filter  # noqa: F401  (conditioned ensembles: reina_model_amd/filtering.py)
 
@@ -54,7 +54,6 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
     final counters are checked as always."""
     from . import engine as _eng
     from . import policy as _pol
-    from . import txlog as _txl
     if summary is not None:
         from . import summary as _summ
         _summ.check_group(summary, contexts, plan, record_history)
@@ -86,25 +85,10 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
         raise ValueError('run_group_plan: `group` is not the group of these contexts')
     for c in contexts:
         c._replayed = True
-    glog = None
-    if all(logged) and logged:
-        glog = contexts[0].transmission_log.device
-        if glog is None or glog.group is not group or any(c.transmission_log.device is not glog for c in contexts):
-            raise ValueError("run_group_plan: the members' transmission logs are not those of this group (logs begun one by "
-                             'one, or with another group, cannot be continued as a group)')
-    elif txlog:
-        for c in contexts:
-            _txl.check_capable(c)
-        glog = _txl.DeviceLog(contexts[0].engine, group=group)
-        for m, c in enumerate(contexts):
-            c.transmission_log = _txl.TransmissionLog(c, device=glog, member=m)
-    if course and glog.course is None:
-        from . import course as _crs
-        if any(c.course_log is not None for c in contexts):
-            raise ValueError("run_group_plan: the members' course logs are not those of this group")
-        gcourse = _crs.DeviceCourse(glog)
-        for m, c in enumerate(contexts):
-            c.course_log = _crs.CourseLog(c, device=gcourse, member=m)
+    glog = _rep.shared_log(contexts, group, "run_group_plan: the members' transmission logs are not those of this group (logs "
+                           'begun one by one, or with another group, cannot be continued as a group)') if any(logged) else None
+    if glog is not None or txlog:
+        glog = _txl.attach_group(contexts, group, glog, course)
     a = group.alloc
     days, start_day = plan['days'], plan['start_day']
     hist = History(days, record_history, group=group)
@@ -377,65 +361,25 @@ def transmission_reports(contexts, age_groups=None, group=None):
     return reps
 
 
-def _logged_group(contexts):
-    """the txlog.DeviceLog these contexts share when they are the whole logged group, in member order; None otherwise"""
-    glog = contexts[0].transmission_log.device
-    if glog is not None and glog.group is not None and all(c.transmission_log.device is glog for c in contexts) \
-            and [c.transmission_log.member for c in contexts] == list(range(glog.members)):
-        return glog
-    return None
-
+# The reports of a log, of every context between the same two days (reports.reports_of_contexts): the members of a logged group
+# (run_group_plan(..., txlog=True[, course=True])) by ONE launch -- one per pass for the lineage report --, contexts that keep
+# logs of their own, and engine libraries without the report's entry points, one by one.
 
 def log_reports(contexts, age_groups=None, n_days=None):
-    """txlog.LogReport of every context, between the same two days.  The members of a logged group (run_group_plan(...,
-    txlog=True)) are reported by ONE launch (reina_group_txlog_report); contexts that keep logs of their own one by one."""
-    from . import txlog as _txl
-    contexts = list(contexts)
-    if any(c.transmission_log is None for c in contexts):
-        raise ValueError('log_reports: a context keeps no transmission log')
-    glog = _logged_group(contexts)
-    if glog is not None:
-        return _txl.report_group(glog, contexts, age_groups, n_days)
-    return [c.transmission_log.report(age_groups, n_days) for c in contexts]
+    """txlog.LogReport of every context (one launch: reina_group_txlog_report)"""
+    return _rep.reports_of_contexts(_txl.LOG, contexts, age_groups, n_days)
 
 
 def lineage_reports(contexts, period=7, n_periods=None, age_groups=None):
-    """lineage.LineageReport of every context, between the same two days.  The members of a logged group (run_group_plan(...,
-    txlog=True)) are reported by ONE launch per pass (reina_group_lineage_report); contexts that keep logs of their own, and
-    engine libraries without the entry points, one by one."""
-    from . import lineage as _lin
-    contexts = list(contexts)
-    if any(c.transmission_log is None for c in contexts):
-        raise ValueError('lineage_reports: a context keeps no transmission log')
-    glog = _logged_group(contexts)
-    if glog is not None and getattr(glog.engine, 'lineage_f', None) is not None:
-        return _lin.report_group(glog, contexts, period, n_periods, age_groups)
-    return [c.transmission_log.lineage_report(period, n_periods, age_groups) for c in contexts]
+    """lineage.LineageReport of every context (one launch per pass: reina_group_lineage_report)"""
+    return _rep.reports_of_contexts(_lin.LINEAGE, contexts, period, n_periods, age_groups)
 
 
 def course_reports(contexts, age_groups=None, n_days=None):
-    """course.CourseReport of every context, between the same two days.  The members of a coursed group (run_group_plan(...,
-    txlog=True, course=True)) are reported by ONE launch (reina_course_report); contexts that keep course logs of their own one
-    by one."""
-    from . import course as _crs
-    contexts = list(contexts)
-    if any(c.course_log is None for c in contexts):
-        raise ValueError('course_reports: a context keeps no course log')
-    glog = _logged_group(contexts)
-    if glog is not None and glog.course is not None and all(c.course_log.device is glog.course for c in contexts):
-        return _crs.report_group(glog.course, contexts, age_groups, n_days)
-    return [c.course_log.report(age_groups, n_days) for c in contexts]
+    """course.CourseReport of every context (one launch: reina_course_report)"""
+    return _rep.reports_of_contexts(_crs.COURSE, contexts, age_groups, n_days)
 
 
 def vaccination_reports(contexts, age_groups=None, n_days=None):
-    """vaccination.VaccinationReport of every context, between the same two days.  The members of a logged group
-    (run_group_plan(..., txlog=True)) are reported by ONE launch (reina_vacc_report); contexts that keep logs of their own, and
-    engine libraries without the entry points, one by one."""
-    from . import vaccination as _vac
-    contexts = list(contexts)
-    if any(c.transmission_log is None for c in contexts):
-        raise ValueError('vaccination_reports: a context keeps no transmission log')
-    glog = _logged_group(contexts)
-    if glog is not None and getattr(glog.engine, 'vacc_f', None) is not None:
-        return _vac.report_group(glog, contexts, age_groups, n_days)
-    return [c.transmission_log.vaccination_report(age_groups, n_days) for c in contexts]
+    """vaccination.VaccinationReport of every context (one launch: reina_vacc_report)"""
+    return _rep.reports_of_contexts(_vac.VACCINATION, contexts, age_groups, n_days)

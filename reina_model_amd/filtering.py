@@ -28,6 +28,7 @@ from datetime import date, datetime
 import numpy as np
 
 from . import engine as _eng
+from . import reports as _rep
 
 FILTER_VERSION = 1              # include/reina_filter.h: REINA_FILTER_VERSION
 CLONE_MAX_PAIRS = 896           # REINA_CLONE_MAX_PAIRS: pairs per launch
@@ -128,19 +129,12 @@ def clone_log_delta_numpy(dst, src, dst_hot, src_hot):
 
 
 def _group_log(contexts, group):
-    """The txlog.DeviceLog of a filter's members: None when none of them keeps a transmission log, the group's log when
-    they are the whole of ONE logged group and that group is `group` (ensemble._logged_group).  A clone carries the log of
-    its group only: members that keep logs of their own, or of another group, are refused."""
-    logged = [getattr(c, 'transmission_log', None) is not None for c in contexts]
-    if not any(logged):
-        return None
-    if all(logged) and group is not None:
-        from . import ensemble
-        glog = ensemble._logged_group(contexts)
-        if glog is not None and glog.group is group:
-            return glog
-    raise ValueError('particle filter: members that keep a transmission log of their own, or of another group, are refused '
-                     "(a clone carries the log of the filter's own group only: particle_filter(..., txlog=True))")
+    """The txlog.DeviceLog of a filter's members (reports.shared_log): None when none of them keeps a transmission log, the
+    group's log when they are the whole of ONE logged group and that group is `group`.  A clone carries the log of its group
+    only: members that keep logs of their own, or of another group, are refused."""
+    return _rep.shared_log(contexts, group, 'particle filter: members that keep a transmission log of their own, or of another '
+                           "group, are refused (a clone carries the log of the filter's own group only: particle_filter(..., "
+                           'txlog=True))')
 
 
 def clone_group(group, pairs, log=None):
@@ -157,7 +151,6 @@ def clone_group(group, pairs, log=None):
             clone_state(_host_arrays(engines[d]), _host_arrays(engines[s]), e0.config.n_agents, mq)
         return
     if log is not None:
-        from . import reports as _rep
         f = _rep.entry_points(e0, 'filter_log_f', 'logged-clone', 'reina_filter_log.h')
         if getattr(log, 'group', None) is not group:
             raise ValueError('clone: `log` is not the transmission log of this group')
@@ -463,39 +456,37 @@ class FilterResult:
         """the group's txlog.DeviceLog of a logged filter, None of an unlogged one"""
         return _group_log(self.contexts, self.group)
 
-    def _logged(self, what, course=False):
+    def _reports(self, kind, *args):
+        """the reports of one kind (reports.Kind) of every final particle (reports.reports_of_contexts)"""
         if self.group is None:
-            raise ValueError('%s: the filter has been closed' % what)
+            raise ValueError('%s: the filter has been closed' % kind.name)
         glog = self.log
         if glog is None:
-            raise ValueError('%s: the filter keeps no transmission log (particle_filter(..., txlog=True))' % what)
-        if course and glog.course is None:
-            raise ValueError('%s: the filter keeps no course log (particle_filter(..., course=True))' % what)
+            raise ValueError('%s: the filter keeps no transmission log (particle_filter(..., txlog=True))' % kind.name)
+        if kind.of == 'course_log' and glog.course is None:
+            raise ValueError('%s: the filter keeps no course log (particle_filter(..., course=True))' % kind.name)
+        return _rep.reports_of_contexts(kind, self.contexts, *args)
 
     def log_reports(self, age_groups=None, n_days=None):
         """txlog.LogReport of every final particle -- of its whole ancestral path -- by one launch (ensemble.log_reports)"""
-        from . import ensemble
-        self._logged('log_reports')
-        return ensemble.log_reports(self.contexts, age_groups, n_days)
+        from .txlog import LOG
+        return self._reports(LOG, age_groups, n_days)
 
     def lineage_reports(self, period=7, n_periods=None, age_groups=None):
         """lineage.LineageReport of every final particle, one launch per pass (ensemble.lineage_reports)"""
-        from . import ensemble
-        self._logged('lineage_reports')
-        return ensemble.lineage_reports(self.contexts, period, n_periods, age_groups)
+        from .lineage import LINEAGE
+        return self._reports(LINEAGE, period, n_periods, age_groups)
 
     def course_reports(self, age_groups=None, n_days=None):
         """course.CourseReport of every final particle by one launch (ensemble.course_reports); needs course=True"""
-        from . import ensemble
-        self._logged('course_reports', course=True)
-        return ensemble.course_reports(self.contexts, age_groups, n_days)
+        from .course import COURSE
+        return self._reports(COURSE, age_groups, n_days)
 
     def vaccination_reports(self, age_groups=None, n_days=None):
         """vaccination.VaccinationReport of every final particle by one launch (ensemble.vaccination_reports): a clone carries
         the cold record, so a particle's days of vaccination are those of its whole ancestral path, like its log"""
-        from . import ensemble
-        self._logged('vaccination_reports')
-        return ensemble.vaccination_reports(self.contexts, age_groups, n_days)
+        from .vaccination import VACCINATION
+        return self._reports(VACCINATION, age_groups, n_days)
 
     def _band_frame(self, values, q, index, means=()):
         import pandas as pd
@@ -598,7 +589,6 @@ def particle_filter(variables, n_particles, observations=None, obs_model=None, w
         raise ValueError('particle_filter: sharded Contexts are not filtered')
     txlog = bool(txlog or course)
     if txlog:
-        from . import reports as _rep
         _rep.entry_points(planner.engine, 'filter_log_f', 'logged-clone', 'reina_filter_log.h')
     if snapshot is not None:
         planner.restore(snapshot, engine_state=False)

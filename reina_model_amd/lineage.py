@@ -282,46 +282,32 @@ class LineageReport(_rep.Report):
 _UNCONVERGED = SCALARS + SCALAR_NAMES.index('unconverged')
 
 
-def _device_words(device_log, table, n_groups, period_days, n_periods):
-    """take(max_depth) of a txlog.DeviceLog for reports.with_deep_pass: one launch per pass for all members"""
-    e = device_log.engine
-    f = _rep.entry_points(e, 'lineage_f', 'lineage-report', 'reina_lineage.h')
-    group = device_log.group is not None
-    name = 'group_lineage_report' if group else 'lineage_report'
-    return lambda depth: _rep.device_words(
-        e, f, name, (device_log._h, table.ctypes.data, int(n_groups), int(period_days), int(n_periods), int(depth or 0)),
-        device_log.members, report_words(n_periods), scratch_bytes(e.config.n_agents), device_log.engines, group)
-
-
 def _arguments(ctx, period, n_periods, age_groups):
     """(table, labels, period_days, n_periods) of a Context's route: its report groups, the periods checked (check_periods)"""
     table, labels = ctx._tx_groups(age_groups)
     return (table, labels) + check_periods(period, n_periods, ctx.day)
 
 
-def report_log(tlog, period=7, n_periods=None, age_groups=None):
-    """TransmissionLog.lineage_report: the library's kernels when it has the entry points and the log is a single engine's on
-    the device, report_numpy on host copies otherwise.  Generations are resolved to the engine's day + 1 first; a state deeper
-    than that (only a synthetic one can be) is reported again with every chain resolved (reports.with_deep_pass)."""
-    ctx = tlog.ctx
-    dlog = tlog.device
-    if dlog is not None and dlog.group is None and getattr(ctx.engine, 'lineage_f', None) is not None:
-        return report_group(dlog, [ctx], period, n_periods, age_groups)[0]
-    table, labels, period, P = _arguments(ctx, period, n_periods, age_groups)
+def _numpy(ctx, tlog, table, params):
+    """report_numpy on host copies, read once for both passes.  Generations are resolved to the engine's day + 1 first; a state
+    deeper than that (only a synthetic one can be) is reported again with every chain resolved (reports.with_deep_pass)."""
     hot, inf, cnt, counters = _rep.host_state(ctx.engine)
     log = tlog.words()
-    take = lambda depth: report_numpy(hot, inf, cnt, log, ctx.age_start, table, period, P,
-                                      depth or _rep.day_depth(counters)).words[None]
-    w = _rep.with_deep_pass(take, _UNCONVERGED, len(hot))[0]
-    return LineageReport(w, period, P, len(labels), labels, ctx.start_date)
+    return lambda depth: report_numpy(hot, inf, cnt, log, ctx.age_start, table, *params, depth or _rep.day_depth(counters)).words
+
+
+LINEAGE = _rep.Kind(
+    name='lineage_reports', of='transmission_log', arguments=_arguments, numpy=_numpy, report=LineageReport,
+    words=lambda period_days, n_periods: report_words(n_periods), names=('lineage_report', 'group_lineage_report'),
+    entry=('lineage_f', 'lineage-report', 'reina_lineage.h'), scratch=scratch_bytes, unconverged=_UNCONVERGED)
+
+
+def report_log(tlog, period=7, n_periods=None, age_groups=None):
+    """TransmissionLog.lineage_report (reports.report_of)"""
+    return _rep.report_of(LINEAGE, tlog, period, n_periods, age_groups)
 
 
 def report_group(device_log, contexts, period=7, n_periods=None, age_groups=None):
     """The reports of every member of a logged group (or of the one engine of a device log): one launch per pass for all
     members (and once more, with every chain resolved, when a member's first pass leaves agents unconverged)."""
-    c0 = contexts[0]
-    table, labels, period, P = _arguments(c0, period, n_periods, age_groups)
-    t8, ng = _rep._group_table(table, c0.nr_ages)
-    take = _device_words(device_log, t8, max(ng, len(labels)), period, P)
-    w = _rep.with_deep_pass(take, _UNCONVERGED, c0.engine.config.n_agents)
-    return [LineageReport(r, period, P, len(labels), labels, c.start_date) for r, c in zip(_rep.member_rows(w), contexts)]
+    return _rep.reports_of_device(LINEAGE, device_log, contexts, period, n_periods, age_groups)

@@ -328,8 +328,9 @@ def _history_or_wait(ctx, hist):
 
 # ------------------------------------------------------------------------------------------------ the device route
 
-class DevicePolicy:
+class DevicePolicy(_eng.Handle):
     """A policy on the device for one engine or one engine group (include/reina_policy.h)."""
+    DESTROY = 'policy_destroy'
 
     def __init__(self, policy, start_date, engine=None, group=None):
         owner = engine if engine is not None else group.engines[0]
@@ -348,17 +349,6 @@ class DevicePolicy:
         else:
             owner._check(self.f['group_policy_create'](group._h, ctypes.byref(rule), ctypes.byref(self._h)), 'group_policy_create')
         self.policy = policy
-
-    def close(self):
-        if self._h:
-            self.f['policy_destroy'](self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def upload_bank(self, tables):
         for level, tab in enumerate(tables):

@@ -3,7 +3,12 @@ csrc/k_addons.inc.  One classification of the links, one age lookup, one forest,
 rule, one device call, one guard for missing entry points and one base for the Report classes -- so that the three
 specifications agree by construction on what a root, a link and a bad link are, as the three kernels do.
 
-Imports engine only; the three report modules import this one, never the other way round.
+And how a report of a log is TAKEN (txlog.py, lineage.py, course.py, vaccination.py): each of those modules declares a Kind,
+and the three routes -- of one log (report_of), of the members of a log on the device (reports_of_device), of a list of
+Contexts (reports_of_contexts) -- and the rule of which group log a list of Contexts shares (group_log, shared_log) are
+written here once.
+
+Imports engine only; the report modules import this one, never the other way round.
 """
 import collections
 import ctypes
@@ -160,6 +165,110 @@ def device_words(engine, f, name, head, members, words, scratch_bytes=None, stal
     engine._check(f[name](*head, rep.data_ptr(), engine.alloc.stream()), name)
     _eng.mark_stale(stale)
     return rep.cpu().numpy().view(np.uint64).reshape(members, words)   # (the copy waits for the launch: the scratch may go)
+
+
+# ------------------------------------------------------------------------------------------------ taking a report of a log
+
+# What is particular to one report taken of a log; its module declares one (txlog.LOG, lineage.LINEAGE, course.COURSE,
+# vaccination.VACCINATION) and binds its public names onto the three routes below.
+#   name         the report's name in refusals ('log_reports')
+#   of           what it is taken of: the Context attribute that holds the log ('transmission_log' or 'course_log')
+#   arguments    (ctx, *args) -> (table, labels, *params): the Context's report groups and the report's own parameters, checked
+#   numpy        (ctx, log, table, params) -> take(max_depth) -> uint64[words]: the specification on host copies
+#   report       the Report class: report(words, *params, n_groups, labels, start_date, *extra)
+#   words        (*params) -> the words of one report
+#   names        the entry points of one engine's log and of a group's (the same twice where the library has one for both)
+#   on           (DeviceLog of a group) -> what of it the entry points take: the log itself, or its course
+#   entry        None: the entry points are those of what it is taken of (there whenever that is on the device); or
+#                (engine attribute, what, header) of entry points of its own, which a library may lack
+#   scratch      (n_agents) -> scratch bytes per member, None without scratch
+#   unconverged  the index of the word that asks for the deep pass (with_deep_pass: max_depth follows the params); None without
+#   extra        (ctx, table) -> further arguments of `report`, the same for every member
+Kind = collections.namedtuple('Kind', 'name of arguments numpy report words names on entry scratch unconverged extra',
+                              defaults=(lambda glog: glog, None, None, None, None))
+
+
+def group_log(contexts):
+    """the txlog.DeviceLog these Contexts share when they are the whole of one logged group, in member order; None otherwise"""
+    logs = [getattr(c, 'transmission_log', None) for c in contexts]
+    glog = logs[0].device if logs and logs[0] is not None else None
+    if glog is not None and glog.group is not None and all(t is not None and t.device is glog for t in logs) \
+            and [t.member for t in logs] == list(range(glog.members)):
+        return glog
+    return None
+
+
+def shared_log(contexts, group, refusal):
+    """The group log of Contexts about to be run or cloned as `group`: None when none of them keeps a transmission log, the
+    group's txlog.DeviceLog when they are the whole of that logged group (group_log), ValueError(refusal) otherwise -- logs
+    kept by some only, logs of their own, or of another group."""
+    if not any(getattr(c, 'transmission_log', None) is not None for c in contexts):
+        return None
+    glog = group_log(contexts)
+    if glog is None or glog.group is not group:
+        raise ValueError(refusal)
+    return glog
+
+
+def _launches(kind, dev):
+    """may the library take this kind of report of `dev` (what a log keeps on the device, or None)"""
+    return dev is not None and (kind.entry is None or getattr(dev.engine, kind.entry[0], None) is not None)
+
+
+def _taken(kind, take, n_agents):
+    return take(None) if kind.unconverged is None else with_deep_pass(take, kind.unconverged, n_agents)
+
+
+def _made(kind, w, contexts, table, labels, params):
+    extra = kind.extra(contexts[0], table) if kind.extra is not None else ()
+    return [kind.report(r, *params, len(labels), labels, c.start_date, *extra) for r, c in zip(member_rows(w), contexts)]
+
+
+def device_take(kind, dev, table, n_groups, params):
+    """take(max_depth) -> uint64[members, words] of `dev`, a txlog.DeviceLog or course.DeviceCourse: one launch for all members"""
+    e = dev.engine
+    f = dev.f if kind.entry is None else entry_points(e, *kind.entry)
+    group = dev.group is not None
+    depth = (lambda d: (int(d or 0),)) if kind.unconverged is not None else (lambda d: ())
+    return lambda d=None: device_words(
+        e, f, kind.names[group], (dev._h, table.ctypes.data, int(n_groups)) + tuple(int(p) for p in params) + depth(d), dev.members,
+        kind.words(*params), kind.scratch(e.config.n_agents) if kind.scratch is not None else None, dev.engines, group)
+
+
+def reports_of_device(kind, dev, contexts, *args):
+    """The reports of the members of `dev` (of a logged group, or of the one engine of a log on the device): one launch for all
+    members, one per pass for a kind that takes the deep pass.  The arguments are checked before `dev` is asked for anything."""
+    c0 = contexts[0]
+    table, labels, *params = kind.arguments(c0, *args)
+    t8, ng = _group_table(table, c0.nr_ages)
+    w = _taken(kind, device_take(kind, dev, t8, max(ng, len(labels)), params), c0.engine.config.n_agents)
+    return _made(kind, w, contexts, table, labels, params)
+
+
+def report_of(kind, log, *args):
+    """The report of one log (a Context's TransmissionLog or CourseLog): the library's kernels when the log is a single engine's
+    on the device and the kind's entry points are there, the specification on host copies otherwise -- oracle B, a log kept in
+    host memory, a member of a group taken on its own."""
+    ctx, dev = log.ctx, log.device
+    if _launches(kind, dev) and dev.group is None:
+        return reports_of_device(kind, dev, [ctx], *args)[0]
+    table, labels, *params = kind.arguments(ctx, *args)
+    take = kind.numpy(ctx, log, table, params)
+    w = _taken(kind, lambda depth: take(depth)[None], ctx.engine.config.n_agents)
+    return _made(kind, w, [ctx], table, labels, params)[0]
+
+
+def reports_of_contexts(kind, contexts, *args):
+    """The reports of a list of Contexts, between the same two days: reports_of_device when they are the whole of one logged
+    group in member order and the library can take the kind of it, report_of one by one otherwise."""
+    contexts = list(contexts)
+    if any(getattr(c, kind.of) is None for c in contexts):
+        raise ValueError('%s: a context keeps no %s' % (kind.name, kind.of.replace('_', ' ')))
+    glog = group_log(contexts)
+    dev = kind.on(glog) if glog is not None else None
+    if _launches(kind, dev) and all(getattr(c, kind.of).device is dev for c in contexts):
+        return reports_of_device(kind, dev, contexts, *args)
+    return [report_of(kind, getattr(c, kind.of), *args) for c in contexts]
 
 
 class Report:

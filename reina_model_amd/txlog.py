@@ -29,7 +29,6 @@ import numpy as np
 
 from . import engine as _eng
 from . import reports as _rep
-from .reports import _group_table
 
 TXLOG_VERSION = 1              # include/reina_txlog.h: REINA_TXLOG_VERSION
 NONE, BEFORE = 0xFFFF, 0xFFFE
@@ -76,6 +75,13 @@ def check_n_days(n_days):
     if not 1 <= int(n_days) <= _eng.MAX_DAYS:
         raise ValueError('n_days must be in [1, %d]' % _eng.MAX_DAYS)
     return int(n_days)
+
+
+def day_arguments(ctx, age_groups, n_days):
+    """(table, labels, n_days) of a report by day: the Context's report groups, and n_days checked (default: the days run so
+    far) -- the argument check of the log, course and vaccination reports"""
+    table, labels = ctx._tx_groups(age_groups)
+    return table, labels, check_n_days(max(int(ctx.day), 1) if n_days is None else n_days)
 
 
 _vp, _u32 = ctypes.c_void_p, ctypes.c_uint32
@@ -284,8 +290,9 @@ def _host_array(t):
     return np.array(t.cpu().numpy() if hasattr(t, 'cpu') else t)
 
 
-class DeviceLog:
+class DeviceLog(_eng.Handle):
     """The library's log of one engine, or of the members of an engine group (include/reina_txlog.h)."""
+    DESTROY = 'txlog_destroy'
 
     def __init__(self, engine, group=None):
         f = _rep.entry_points(engine, 'txlog_f', 'transmission-log', 'reina_txlog.h')
@@ -298,18 +305,9 @@ class DeviceLog:
         else:
             engine._check(f['group_txlog_create'](group._h, engine.alloc.stream(), ctypes.byref(self._h)), 'group_txlog_create')
 
-    def close(self):
+    def _closing(self):
         if self.course is not None:
             self.course.close()
-        if self._h:
-            self.f['txlog_destroy'](self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def engines(self):
@@ -340,12 +338,6 @@ class DeviceLog:
         if len(w) != self.engine.config.n_agents:
             raise ValueError('a log has one word per agent')
         self.engine._check(self.f['txlog_write'](self._h, int(member), w.ctypes.data, self.engine.alloc.stream()), 'txlog_write')
-
-    def report_words(self, table, n_groups, n_days):
-        """[members, report_words(n_days)] uint64: one launch for all members"""
-        name = 'txlog_report' if self.group is None else 'group_txlog_report'
-        return _rep.device_words(self.engine, self.f, name, (self._h, table.ctypes.data, int(n_groups), int(n_days)), self.members,
-                                 report_words(n_days), stale=self.engines, group=self.group is not None)
 
 
 class TransmissionLog:
@@ -403,13 +395,7 @@ class TransmissionLog:
 
     def report(self, age_groups=None, n_days=None):
         """LogReport of the days [0, n_days) (default: the days run so far)"""
-        ctx = self.ctx
-        if self.device is not None and self.device.group is None:
-            return report_group(self.device, [ctx], age_groups, n_days)[0]
-        table, labels = ctx._tx_groups(age_groups)
-        n_days = check_n_days(max(int(ctx.day), 1) if n_days is None else n_days)
-        w = report_numpy(*_rep.host_state(ctx.engine)[:3], self.words(), ctx.age_start, table, n_days).words
-        return LogReport(w, n_days, len(labels), labels, ctx.start_date)
+        return _rep.report_of(LOG, self, age_groups, n_days)
 
     def lineage_report(self, period=7, n_periods=None, age_groups=None):
         """lineage.LineageReport between two days: who infects whom by period of `period` days, and the trees of the run by
@@ -488,11 +474,33 @@ def run_host_driven(ctx, days, record_history=True, on_day=None):
     return np.stack(rows) if record_history and rows else (np.zeros((0, _eng.COUNTER_WORDS), dtype=np.int32) if record_history else None)
 
 
+LOG = _rep.Kind(
+    name='log_reports', of='transmission_log', arguments=day_arguments, report=LogReport, words=report_words,
+    numpy=lambda ctx, log, table, params: lambda depth: report_numpy(*_rep.host_state(ctx.engine)[:3], log.words(), ctx.age_start,
+                                                                      table, *params).words,
+    names=('txlog_report', 'group_txlog_report'))
+
+
 def report_group(device_log, contexts, age_groups=None, n_days=None):
     """The reports of every member of a logged group (or of the one engine of a device log): one launch for all members."""
-    c0 = contexts[0]
-    table, labels = c0._tx_groups(age_groups)
-    n_days = check_n_days(max(int(c0.day), 1) if n_days is None else n_days)
-    t8, ng = _group_table(table, c0.nr_ages)
-    w = device_log.report_words(t8, max(ng, len(labels)), n_days)
-    return [LogReport(r, n_days, len(labels), labels, c.start_date) for r, c in zip(_rep.member_rows(w), contexts)]
+    return _rep.reports_of_device(LOG, device_log, contexts, age_groups, n_days)
+
+
+def attach_group(contexts, group, glog=None, course=False):
+    """The txlog.DeviceLog of `group` with every member attached to it: `glog` when the members keep it already
+    (reports.shared_log), otherwise a log begun here, every Context getting its TransmissionLog.  `course`: the group's course log
+    too, begun here unless the log has one, every Context getting its CourseLog."""
+    if glog is None:
+        for c in contexts:
+            check_capable(c)
+        glog = DeviceLog(contexts[0].engine, group=group)
+        for m, c in enumerate(contexts):
+            c.transmission_log = TransmissionLog(c, device=glog, member=m)
+    if course and glog.course is None:
+        from . import course as _crs
+        if any(c.course_log is not None for c in contexts):
+            raise ValueError("run_group_plan: the members' course logs are not those of this group")
+        gcourse = _crs.DeviceCourse(glog)
+        for m, c in enumerate(contexts):
+            c.course_log = _crs.CourseLog(c, device=gcourse, member=m)
+    return glog

@@ -289,42 +289,28 @@ class VaccinationReport(_rep.Report):
 
 # ------------------------------------------------------------------------------------------------ routes
 
-def _arguments(ctx, age_groups, n_days):
-    table, labels = ctx._tx_groups(age_groups)
-    return table, labels, check_n_days(max(int(ctx.day), 1) if n_days is None else n_days)
-
-
 def _sizes(ctx, table):
     return group_sizes(ctx.age_start, _group_table(table, ctx.nr_ages)[0], ctx.nr_ages)
 
 
+VACCINATION = _rep.Kind(
+    name='vaccination_reports', of='transmission_log', arguments=_txl.day_arguments, report=VaccinationReport, words=report_words,
+    numpy=lambda ctx, tlog, table, params: lambda depth: report_numpy(
+        _rep.host_state(ctx.engine)[0], _txl._host_array(ctx.engine.tensors['vacc_day']), tlog.words(), ctx.age_start, table, *params).words,
+    names=('vacc_report', 'vacc_report'), entry=('vacc_f', 'vaccination-report', 'reina_vaccination.h'),
+    extra=lambda ctx, table: (_sizes(ctx, table),))
+
+
 def device_report_words(device_log, table, n_groups, n_days):
     """[members, report_words(n_days)] uint64 of a txlog.DeviceLog: one launch for all members"""
-    e = device_log.engine
-    f = _rep.entry_points(e, 'vacc_f', 'vaccination-report', 'reina_vaccination.h')
-    return _rep.device_words(e, f, 'vacc_report', (device_log._h, table.ctypes.data, int(n_groups), int(n_days)), device_log.members,
-                             report_words(n_days), stale=device_log.engines)
+    return _rep.device_take(VACCINATION, device_log, table, n_groups, (n_days,))()
 
 
 def report_log(tlog, age_groups=None, n_days=None):
-    """TransmissionLog.vaccination_report: the library's kernel when it has the entry points and the log is a single engine's
-    on the device, report_numpy on host copies otherwise (oracle B, a host-kept log, a member of a group on its own)."""
-    ctx = tlog.ctx
-    dlog = tlog.device
-    if dlog is not None and dlog.group is None and getattr(ctx.engine, 'vacc_f', None) is not None:
-        return report_group(dlog, [ctx], age_groups, n_days)[0]
-    table, labels, n_days = _arguments(ctx, age_groups, n_days)
-    hot = _rep.host_state(ctx.engine)[0]
-    vd = _txl._host_array(ctx.engine.tensors['vacc_day'])
-    w = report_numpy(hot, vd, tlog.words(), ctx.age_start, table, n_days).words
-    return VaccinationReport(w, n_days, len(labels), labels, ctx.start_date, _sizes(ctx, table))
+    """TransmissionLog.vaccination_report (reports.report_of)"""
+    return _rep.report_of(VACCINATION, tlog, age_groups, n_days)
 
 
 def report_group(device_log, contexts, age_groups=None, n_days=None):
     """The reports of every member of a logged group (or of the one engine of a device log): one launch for all members."""
-    c0 = contexts[0]
-    table, labels, n_days = _arguments(c0, age_groups, n_days)
-    t8, ng = _group_table(table, c0.nr_ages)
-    w = device_report_words(device_log, t8, max(ng, len(labels)), n_days)
-    sizes = _sizes(c0, table)
-    return [VaccinationReport(r, n_days, len(labels), labels, c.start_date, sizes) for r, c in zip(_rep.member_rows(w), contexts)]
+    return _rep.reports_of_device(VACCINATION, device_log, contexts, age_groups, n_days)

@@ -9,6 +9,7 @@ import numpy as np
 
 import tx_util
 from filter_util import small_scenario
+from tx_util import assert_words  # noqa: F401  (course_util.assert_words: the one of every report util)
 from reina_model_amd import course as crs
 from reina_model_amd import txlog as txl
 
@@ -157,13 +158,6 @@ def walk_report(hot, log, rec, age_start, age_group, n_days):
                         tables.ravel(), cohort.ravel()])
     assert len(w) == crs.report_words(n_days)
     return w
-
-
-def assert_words(got, want):
-    got, want = np.asarray(got, dtype=np.uint64), np.asarray(want, dtype=np.uint64)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    bad = np.flatnonzero(got != want)
-    assert not len(bad), [(int(k), int(got[k]), int(want[k])) for k in bad[:8]]
 
 
 def cut_records(full, cut, hot_at_cut):

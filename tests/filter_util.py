@@ -32,7 +32,8 @@ def observations(hist, start_date, rows, streams=('all_detected', 'in_ward')):
 
 
 def carried(engine):
-    """the carried arrays of an engine (host copies, uint32; cold / infectees as [n, 8])"""
+    """the carried arrays of an engine (host copies, uint32; cold / infectees as [n, 8]).  Stays beside reports.host_state on
+    purpose: the clone is checked on every buffer a day carries, read here by name with nothing of the package in between."""
     n = engine.config.n_agents
     out = {}
     for name in ('hot', 'cold', 'infectees', 'counters', 'control', 'queue0', 'queue1', 'level1', 'active_bits', 'infected_bits'):

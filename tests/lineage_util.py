@@ -6,6 +6,7 @@ import bisect
 
 import numpy as np
 
+from tx_util import assert_words  # noqa: F401  (lineage_util.assert_words: the one of every report util)
 from reina_model_amd import lineage as lin
 from reina_model_amd import transmission as tx
 from reina_model_amd import txlog as txl
@@ -97,13 +98,6 @@ def walk_report(hot, infector, log, age_start, age_group, period_days, n_periods
                         seed.ravel(), tree_sizes.ravel(), cohort.ravel(), lineage.ravel(), mixing_t.ravel(), mixing_c.ravel()])
     assert len(w) == lin.report_words(P)
     return w
-
-
-def assert_words(got, want):
-    got, want = np.asarray(got, dtype=np.uint64), np.asarray(want, dtype=np.uint64)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    bad = np.flatnonzero(got != want)
-    assert not len(bad), [(int(k), int(got[k]), int(want[k])) for k in bad[:8]]
 
 
 def cycle_state():

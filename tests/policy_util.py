@@ -91,7 +91,8 @@ def first_escalation(levels):
 
 
 def hot_cold(ctx):
-    """(hot words, cold records' infector / n_infected / onset / vacc_day) of a Context's engine, host copies"""
+    """(hot words, cold records' infector / n_infected / onset / vacc_day) of a Context's engine, host copies.  Stays beside
+    reports.host_state on purpose: that one hands out two of the four cold fields, and this compares whole runs by all four."""
     n = ctx.engine.config.n_agents
     out = []
     for name in ('hot', 'cold'):

@@ -178,6 +178,14 @@ def walk_report(hot, infector, n_infected, age_start, age_group, max_depth):
     return w
 
 
+def assert_words(got, want):
+    """two reports' words are the same; the first differing ones otherwise (every report util's assert_words)"""
+    got, want = np.asarray(got, dtype=np.uint64), np.asarray(want, dtype=np.uint64)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    bad = np.flatnonzero(got != want)
+    assert not len(bad), [(int(k), int(got[k]), int(want[k])) for k in bad[:8]]
+
+
 def put_forest(ctx, hot, infector, n_infected, day=None):
     """write a forest into a Context's engine (numpy or torch tensors); `day`: the counter block's REINA_S_DAY word"""
     t = ctx.engine.tensors

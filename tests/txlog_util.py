@@ -9,7 +9,9 @@ from datetime import date
 import numpy as np
 
 import tx_util
+from tx_util import assert_words  # noqa: F401  (txlog_util.assert_words: the one of every report util)
 from reina_model_amd import engine as eng
+from reina_model_amd import reports
 from reina_model_amd import txlog as txl
 
 SIZES = (1, 511, 512, 513, 3 * 512 + 7)
@@ -170,13 +172,6 @@ def walk_report(hot, infector, n_infected, log, age_start, age_group, n_days):
     return w
 
 
-def assert_words(got, want, n_days=None):
-    got, want = np.asarray(got, dtype=np.uint64), np.asarray(want, dtype=np.uint64)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    bad = np.flatnonzero(got != want)
-    assert not len(bad), [(int(k), int(got[k]), int(want[k])) for k in bad[:8]]
-
-
 def record_by_hot(log, hot, day):
     """what k_txlog_day's hot-word form stores on a day that follows a recorded day: an ACTIVE agent in INCUBATION with the day
     in bits 24-31 gets the whole word NONE << 16 | day, one in ILLNESS with day + 1 there the day in its upper half; nothing else
@@ -238,11 +233,10 @@ def new_infections(hist, final_counters):
 
 
 def host_state(ctx):
-    """(hot, infector, n_infected) of a Context's engine, host copies"""
-    n = ctx.engine.config.n_agents
-    g = lambda name: (lambda t: np.array(t.cpu().numpy() if hasattr(t, 'cpu') else t).view(np.uint32))(ctx.engine.tensors[name])
-    cold = g('cold').reshape(n, eng.COLD_WORDS)
-    return g('hot'), cold[:, 2].view(np.int32), cold[:, 3].view(np.int32)
+    """(hot, infector, n_infected) of a Context's engine, host copies (reports.host_state, which hands out views of a
+    host-memory engine's buffers)"""
+    hot, infector, n_infected, _ = reports.host_state(ctx.engine)
+    return hot.copy(), infector.view(np.int32).copy(), n_infected.view(np.int32).copy()
 
 
 def spec_report(ctx, log_words, n_days=None, groups=None):

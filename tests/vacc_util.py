@@ -11,7 +11,9 @@ import numpy as np
 import tx_util
 import txlog_util
 from filter_util import small_scenario
+from tx_util import assert_words  # noqa: F401  (vacc_util.assert_words: the one of every report util)
 from reina_model_amd import engine as eng
+from reina_model_amd import reports
 from reina_model_amd import txlog as txl
 from reina_model_amd import vaccination as vac
 
@@ -195,18 +197,13 @@ def walk_report(hot, vacc_day, log, age_start, age_group, n_days):
     return w
 
 
-def assert_words(got, want):
-    got, want = np.asarray(got, dtype=np.uint64), np.asarray(want, dtype=np.uint64)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    bad = np.flatnonzero(got != want)
-    assert not len(bad), [(int(k), int(got[k]), int(want[k])) for k in bad[:8]]
-
-
 def host_arrays(ctx):
-    """(hot uint32[N], vacc_day int32[N]) of a Context's engine, host copies"""
-    g = lambda name: (lambda t: np.array(t.cpu().numpy() if hasattr(t, 'cpu') else t))(ctx.engine.tensors[name])
-    n = ctx.engine.config.n_agents
-    return g('hot').view(np.uint32), g('cold').view(np.int32).reshape(n, eng.COLD_WORDS)[:, eng.COLD_FIELDS['vacc_day']].copy()
+    """(hot uint32[N], vacc_day int32[N]) of a Context's engine, host copies.  The hot words as reports.host_state reads them;
+    vacc_day deliberately its own way, word 5 of the cold records and not the engine's strided view that the report's route
+    reads (engine.tensors['vacc_day']): an independent check of that view."""
+    t = ctx.engine.tensors['cold']
+    cold = np.array(t.cpu().numpy() if hasattr(t, 'cpu') else t).view(np.int32).reshape(ctx.engine.config.n_agents, eng.COLD_WORDS)
+    return reports.host_state(ctx.engine)[0].copy(), cold[:, eng.COLD_FIELDS['vacc_day']].copy()
 
 
 def spec_report(ctx, n_days=None, groups=None, log_words=None):
