@@ -13,16 +13,182 @@ engine instances side by side, every member owning its HBM state.  Two ways to i
 
 Members are fully independent (BASELINE config 5: "replicas only", no collective); over several
 GPUs the seeds are simply partitioned across ranks.  Results are bit-identical either way and
-identical to running each seed alone (tests/test_parity_gpu.py).
+identical to running each seed alone (tests/test_parity_gpu.py).  How an ensemble is set up -- planner, members,
+group -- is stated once, ahead of the routes (DESIGN.md "How an ensemble is set up").
 """
+import ctypes
+import os
 import threading
+import time
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import course as _crs, lineage as _lin, reports as _rep, simulation, txlog as _txl, vaccination as _vac
+from . import (course as _crs, engine as _eng, lineage as _lin, policy as _pol, reports as _rep, simulation, snapshot as _snap,
+               summary as _summ, transmission as _tx, txlog as _txl, vaccination as _vac)
 from .dayrun import History, replay_plan
 from .filtering import particle_filter  # noqa: F401  (conditioned ensembles: reina_model_amd/filtering.py)
+
+
+class Setup:
+    """What every Context of one ensemble is made with -- the same five keywords of simulation.make_context on every route --
+    and, for the futures of one realised past, the snapshot.Snapshot they start from."""
+
+    def __init__(self, age_counts=None, device='cuda:0', engine_factory=None, interventions=None, ipc=None, snapshot=None):
+        self.kw = dict(age_counts=age_counts, device=device, engine_factory=engine_factory, interventions=interventions, ipc=ipc)
+        self.snapshot = snapshot
+
+    def context(self, variables, seed):
+        """One member: a Context of `variables`; with a snapshot, restored on the HOST only (its checks and the scenario's
+        state: the engines of all members are brought to it by one launch, restore_group)."""
+        c = simulation.make_context(variables, seed=seed, **self.kw)
+        if self.snapshot is not None:
+            c.restore(self.snapshot, engine_state=False)
+        return c
+
+    def planner(self, variables, seed, policy=None):
+        """A Context that only makes plans (its engine runs no day).  Under a policy the mask shares of the snapshot's last upload
+        are replayed into it: the level tables start from them.  (particle_filter does without the replay: it takes no policy.)"""
+        p = self.context(variables, seed)
+        if policy is not None and self.snapshot is not None:
+            p._packed_tables_for_restore(self.snapshot.state)
+        return p
+
+    def members(self, variables, seeds, member_variables=None):
+        """One Context per seed, of `variables` or of member_variables[m]"""
+        vs = member_variables if member_variables is not None else [variables] * len(seeds)
+        return [self.context(v, sd) for v, sd in zip(vs, seeds)]
+
+    def restore_group(self, group, contexts):
+        """Brings the group of `contexts` to the snapshot, when there is one: the image unpacked into all members by one launch
+        (reina_group_snap_unpack), then every member's contact tables as of the snapshot's day."""
+        if self.snapshot is not None:
+            _snap.unpack_group(group, contexts[0]._disease, self.snapshot.image)
+            for c in contexts:
+                c.engine.upload_contact_tables(*c._packed_tables_for_restore(self.snapshot.state))
+
+
+def group_for(contexts, group=None, route=None):
+    """(group, made here): the caller's `group`, checked to be that of exactly these contexts' engines, or one made here"""
+    if group is None:
+        return _eng.EngineGroup([c.engine for c in contexts]), True
+    if [e._h.value for e in group.engines] != [c.engine._h.value for c in contexts]:
+        raise ValueError('%s: `group` is not the group of these contexts' % route)
+    return group, False
+
+
+def check_shared_days(plans, what):
+    """Plans that share a group share their day descriptors: refuses the first `what` ('scenario', 'branch') whose plan differs
+    from plan 0 in them.  (Plans that are the same object need no look.)"""
+    words = lambda p: [(n, ctypes.string_at(a, ctypes.sizeof(a))) for _, a, n in p['segments']]
+    for k, p in enumerate(plans[1:], 1):
+        if p is not plans[0] and words(p) != words(plans[0]):
+            raise ValueError('%s %d differs from %s 0 in more than the values of its mobility / mask '
+                             'interventions: it cannot share a group' % (what, k, what))
+
+
+def plan_once(setup, variables, seed, days, summary=None):
+    """(plan, pending) of a run in chunks of members: the plan, made ONCE by a planner that goes at once -- the day descriptors
+    do not depend on the seed --, and with `summary` (summary.SummarySpec) the summary.Pending of the chunks' rows, else None"""
+    planner = setup.planner(variables, seed)
+    plan = planner.make_plan(days)
+    return plan, (_summ.Pending(summary, planner, plan['start_day']) if summary is not None else None)
+
+
+def chunks(seeds, size):
+    return [seeds[start:start + size] for start in range(0, len(seeds), size)]
+
+
+def _stopwatch(route):
+    """REINA_ENS_TIMING (diagnostic: tools/ens_first_run2.py): mark(name) takes the time, the last prints where the time went"""
+    marks = [('start', time.perf_counter())] if os.environ.get('REINA_ENS_TIMING') else None
+
+    def mark(name, last=False):
+        if marks is not None:
+            marks.append((name, time.perf_counter()))
+            if last:
+                print(route + ': ' + ' | '.join('%s %.1f ms' % (n, (t - marks[k][1]) * 1e3) for k, (n, t) in enumerate(marks[1:])), flush=True)
+    return mark
+
+
+def _refuse_group_plan(contexts, plan, record_history, member_plans, policy, txlog, summary):
+    """what run_group_plan refuses before anything runs"""
+    if summary is not None:
+        _summ.check_group(summary, contexts, plan, record_history)
+    logged = [c.transmission_log is not None for c in contexts]
+    if (txlog or any(logged)) and policy is not None:
+        raise ValueError('run_group_plan: a transmission log and a policy cannot be combined')
+    if any(logged) and not all(logged):
+        raise ValueError('run_group_plan: some members keep a transmission log and some do not')
+    if policy is not None:
+        if member_plans is not None:
+            raise ValueError('run_group_plan: a policy and member_plans (a sweep) cannot be combined')
+        if plan.get('policy') is not policy or plan.get('policy_banks') is None:
+            raise ValueError('run_group_plan: the plan must be made with the policy (make_plan(days, policy=...))')
+        for c in contexts:
+            _pol.check_capable(c)
+
+
+def _group_and_log(contexts, group, txlog, course):
+    """(group, made here, the group's txlog.DeviceLog or None): the group of a logged group's log when none is given (the log
+    keeps its group open), else group_for; the members' log continued, or begun with `txlog`."""
+    logged = bool(contexts) and contexts[0].transmission_log is not None   # (all or none: _refuse_group_plan)
+    if group is None and logged and contexts[0].transmission_log.device is not None:
+        group = contexts[0].transmission_log.device.group
+    group, own_group = group_for(contexts, group, 'run_group_plan')
+    for c in contexts:
+        c._replayed = True
+    glog = _rep.shared_log(contexts, group, "run_group_plan: the members' transmission logs are not those of this group (logs "
+                           'begun one by one, or with another group, cannot be continued as a group)') if logged else None
+    if glog is not None or txlog:
+        glog = _txl.attach_group(contexts, group, glog, course)
+    return group, own_group, glog
+
+
+def _replay_group_plan(contexts, plan, member_plans, group, glog, policy, hist):
+    """The plan's days issued to the group -- through the policy.DevicePolicy of a policy (returned, else None), through the
+    group's log, or to the group itself; a sweep's members get their own tables at every table change."""
+    if policy is not None:
+        dev = _pol.DevicePolicy(policy, contexts[0].start_date, group=group)
+        replay_plan(plan, dev, hist, lambda si, tables: dev.upload_bank(plan['policy_banks'][si][0]))
+        return dev
+
+    def upload_member_tables(si, tables):   # (a sweep: every member its own)
+        for c, mp in zip(contexts, member_plans):
+            if mp['segments'][si][0] is not None:
+                c.engine.upload_contact_tables(*mp['segments'][si][0])
+
+    def upload_group_tables(si, tables):
+        if tables is not None:
+            group.upload_contact_tables(*tables)
+
+    replay_plan(plan, glog if glog is not None else group, hist, upload_member_tables if member_plans is not None else upload_group_tables)
+
+
+def _end_group_plan(contexts, plan, member_plans, dev, hist, summary, alloc, mark):
+    """The members' end: under a policy (dev) their levels from the trace (the run's wait; their host-side table mirrors follow
+    them), their day and mobility factors, the history or its summary (returned), and SimulationFailed for a problem word."""
+    days, start_day = plan['days'], plan['start_day']
+    if dev is not None:
+        trace = dev.read_trace(start_day, days)
+        dev.close()
+        seg_of_day, factors = _pol.plan_segments_of_days(plan), [b[1] for b in plan['policy_banks']]
+    for m, c in enumerate(contexts):
+        if dev is not None:
+            _pol._end_device_run(c, trace, m, start_day, plan['mobility_history'][0] if days else 0.0, seg_of_day, factors)
+        else:
+            c.mobility_history = (member_plans[m] if member_plans is not None else plan)['mobility_history']
+        c.day = start_day + days
+    out = hist.to_host() if summary is None else _summ.of_group(summary, hist.rows(), contexts, start_day)
+    mark('history on the host')
+    torch = getattr(alloc, 'torch', None)
+    # on the device the members' final counter blocks (the problem word among them) in one copy instead of one per member (4 ms for 128)
+    finals = (alloc.to_host(torch.stack([c.engine.tensors['counters'] for c in contexts])) if torch is not None else
+              [c.engine.read_counters() for c in contexts])
+    for c, final in zip(contexts, finals):
+        c._raise_on_problem(np.asarray(final))
+    mark('final counters')
+    return out
 
 
 def run_group_plan(contexts, plan, record_history=True, member_plans=None, group=None, policy=None, txlog=False, summary=None, course=False):
@@ -52,104 +218,18 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
     `summary` (summary.SummarySpec): an EnsembleSummary (quantile bands, peaks, exceedance: reina_model_amd/summary.py) is
     returned in place of the history, computed where the rows are: a device group's rows are never read back.  The members'
     final counters are checked as always."""
-    from . import engine as _eng
-    from . import policy as _pol
-    if summary is not None:
-        from . import summary as _summ
-        _summ.check_group(summary, contexts, plan, record_history)
     txlog = txlog or course
-    logged = [c.transmission_log is not None for c in contexts]
-    if (txlog or any(logged)) and policy is not None:
-        raise ValueError('run_group_plan: a transmission log and a policy cannot be combined')
-    if any(logged) and not all(logged):
-        raise ValueError('run_group_plan: some members keep a transmission log and some do not')
-    if policy is not None:
-        if member_plans is not None:
-            raise ValueError('run_group_plan: a policy and member_plans (a sweep) cannot be combined')
-        if plan.get('policy') is not policy or plan.get('policy_banks') is None:
-            raise ValueError('run_group_plan: the plan must be made with the policy (make_plan(days, policy=...))')
-        for c in contexts:
-            _pol.check_capable(c)
-    import os as _os, time as _time
-    _T = [] if _os.environ.get('REINA_ENS_TIMING') else None   # (diagnostic: where a group run's wall time goes, tools/ens_first_run2.py)
-    def _t(name):
-        if _T is not None:
-            _T.append((name, _time.perf_counter()))
-    _t('start')
-    if group is None and logged and all(logged) and contexts[0].transmission_log.device is not None:
-        group = contexts[0].transmission_log.device.group   # (a logged group's log keeps its group open)
-    own_group = group is None
-    if own_group:
-        group = _eng.EngineGroup([c.engine for c in contexts])
-    elif [e._h.value for e in group.engines] != [c.engine._h.value for c in contexts]:
-        raise ValueError('run_group_plan: `group` is not the group of these contexts')
-    for c in contexts:
-        c._replayed = True
-    glog = _rep.shared_log(contexts, group, "run_group_plan: the members' transmission logs are not those of this group (logs "
-                           'begun one by one, or with another group, cannot be continued as a group)') if any(logged) else None
-    if glog is not None or txlog:
-        glog = _txl.attach_group(contexts, group, glog, course)
-    a = group.alloc
-    days, start_day = plan['days'], plan['start_day']
-    hist = History(days, record_history, group=group)
-    dev = _pol.DevicePolicy(policy, contexts[0].start_date, group=group) if policy is not None else None
-
-    def upload_bank(si, tables):
-        dev.upload_bank(plan['policy_banks'][si][0])
-
-    def upload_member_tables(si, tables):   # (a sweep: every member its own)
-        for c, mp in zip(contexts, member_plans):
-            if mp['segments'][si][0] is not None:
-                c.engine.upload_contact_tables(*mp['segments'][si][0])
-
-    def upload_group_tables(si, tables):
-        if tables is not None:
-            group.upload_contact_tables(*tables)
-
-    if dev is not None:
-        replay_plan(plan, dev, hist, upload_bank)
-    else:
-        replay_plan(plan, glog if glog is not None else group, hist,
-                    upload_member_tables if member_plans is not None else upload_group_tables)
-    _t('issued')
-    if dev is not None:
-        trace = dev.read_trace(start_day, days)   # (the run's wait; the members' host-side table mirrors follow their levels)
-        dev.close()
-        seg_of_day, factors = _pol.plan_segments_of_days(plan), [b[1] for b in plan['policy_banks']]
-    for m, c in enumerate(contexts):
-        if dev is not None:
-            _pol._end_device_run(c, trace, m, start_day, plan['mobility_history'][0] if days else 0.0, seg_of_day, factors)
-        else:
-            c.mobility_history = (member_plans[m] if member_plans is not None else plan)['mobility_history']
-        c.day = start_day + days
-    out = hist.to_host() if summary is None else _summ.of_group(summary, hist.rows(), contexts, start_day)
-    _t('history on the host')
-    torch = getattr(a, 'torch', None)
-    if torch is not None:
-        # the members' final counter blocks (the problem word among them) in one copy instead of one per member (4 ms for 128)
-        finals = a.to_host(torch.stack([c.engine.tensors['counters'] for c in contexts]))
-        for m, c in enumerate(contexts):
-            c._raise_on_problem(np.asarray(finals[m]))
-    else:
-        for c in contexts:
-            c._raise_on_problem(c.engine.read_counters())
-    _t('final counters')
+    _refuse_group_plan(contexts, plan, record_history, member_plans, policy, txlog, summary)
+    mark = _stopwatch('run_group_plan')
+    group, own_group, glog = _group_and_log(contexts, group, txlog, course)
+    hist = History(plan['days'], record_history, group=group)
+    dev = _replay_group_plan(contexts, plan, member_plans, group, glog, policy, hist)
+    mark('issued')
+    out = _end_group_plan(contexts, plan, member_plans, dev, hist, summary, group.alloc, mark)
     if own_group and glog is None:   # (a group made here for a logged run stays open with its log, and goes with it)
         group.close()
-    _t('closed')
-    if _T is not None:
-        print('run_group_plan: ' + ' | '.join('%s %.1f ms' % (n, (t - _T[k][1]) * 1e3) for k, (n, t) in enumerate(_T[1:])), flush=True)
+    mark('closed', last=True)
     return out
-
-
-def _same_day_descriptors(p, q):
-    import ctypes
-    if len(p['segments']) != len(q['segments']):
-        return False
-    for (_, a, n), (_, b, m) in zip(p['segments'], q['segments']):
-        if n != m or ctypes.string_at(a, ctypes.sizeof(a)) != ctypes.string_at(b, ctypes.sizeof(b)):
-            return False
-    return True
 
 
 def run_sweep(variables_list, seeds, days, age_counts=None, device='cuda:0', engine_factory=None, ipc='auto'):
@@ -159,16 +239,10 @@ def run_sweep(variables_list, seeds, days, age_counts=None, device='cuda:0', eng
     limit-mobility / wear-masks interventions; they may differ in those interventions' values (each member
     gets its own contact tables).  Returns (history[len(seeds), days, COUNTER_WORDS], contexts)."""
     assert len(variables_list) == len(seeds)
-    plans, ctxs = [], []
-    for v, sd in zip(variables_list, seeds):
-        planner = simulation.make_context(v, age_counts=age_counts, seed=sd, device=device, engine_factory=engine_factory, ipc=ipc)
-        plans.append(planner.make_plan(days))
-        del planner
-        ctxs.append(simulation.make_context(v, age_counts=age_counts, seed=sd, device=device, engine_factory=engine_factory, ipc=ipc))
-    for k, p in enumerate(plans[1:], 1):
-        if not _same_day_descriptors(plans[0], p):
-            raise ValueError('scenario %d differs from scenario 0 in more than the values of its mobility / mask '
-                             'interventions: it cannot share a group' % k)
+    setup = Setup(age_counts, device, engine_factory, None, ipc)
+    plans = [setup.planner(v, sd).make_plan(days) for v, sd in zip(variables_list, seeds)]
+    ctxs = setup.members(None, seeds, variables_list)
+    check_shared_days(plans, 'scenario')
     return run_group_plan(ctxs, plans[0], member_plans=plans), ctxs
 
 
@@ -185,10 +259,7 @@ def run_ensemble_distributed(variables, seeds, days, group=None, concurrent=64, 
     dist.gather_object((mine, hist), parts, dst=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
     if rank != 0:
         return None
-    by_seed = {}
-    for sds, h in parts:
-        for k, sd in enumerate(sds):
-            by_seed[sd] = h[k]
+    by_seed = {sd: h[k] for sds, h in parts for k, sd in enumerate(sds)}
     return np.stack([by_seed[sd] for sd in seeds])
 
 
@@ -200,62 +271,39 @@ def run_ensemble(variables, seeds, days, age_counts=None, device='cuda:0', threa
     one simulate_individuals applies for these variables (calc/simulation.py:152), None = none.
     `summary` (summary.SummarySpec): the EnsembleSummary of all seeds instead of the history -- the chunks' histories stay on
     the device until the last has run and are summarised in one call; the threaded route summarises on the host."""
-    import torch
     seeds = list(seeds)
     concurrent = len(seeds) if concurrent is None else max(1, int(concurrent))
+    # (the threaded route has always made its Contexts with the library's own engines: `engine_factory` is the batched route's)
+    setup = Setup(age_counts, device, engine_factory if batched else None, interventions, ipc)
+    plan, pending = plan_once(setup, variables, seeds[0], days, summary)
     if batched:
-        planner = simulation.make_context(variables, age_counts=age_counts, seed=seeds[0], device=device,
-                                          interventions=interventions, engine_factory=engine_factory, ipc=ipc)
-        plan = planner.make_plan(days)
-        pending = None
-        if summary is not None:
-            from . import summary as _summ
-            pending = _summ.Pending(summary, planner, plan['start_day'])
-        del planner
-        outs = []
-        for start in range(0, len(seeds), concurrent):
-            ctxs = [simulation.make_context(variables, age_counts=age_counts, seed=sd, device=device,
-                                            interventions=interventions, engine_factory=engine_factory, ipc=ipc)
-                    for sd in seeds[start:start + concurrent]]
-            outs.append(run_group_plan(ctxs, plan, summary=pending))
-            del ctxs
+        outs = [run_group_plan(setup.members(variables, part), plan, summary=pending) for part in chunks(seeds, concurrent)]
+    else:
+        outs = [_run_threaded(setup, variables, part, plan, device, threads) for part in chunks(seeds, concurrent)]
         if pending is not None:
-            return pending.finish(members=seeds)
-        return np.concatenate(outs)
-    out = [None] * len(seeds)
+            pending.add(np.concatenate(outs))
+    return pending.finish(members=seeds) if pending is not None else np.concatenate(outs)
+
+
+def _run_threaded(setup, variables, seeds, plan, device, threads):
+    """history [len(seeds), days, COUNTER_WORDS] of the members of `seeds`, each on a HIP stream of its own, their days issued
+    by a pool of host threads"""
+    import torch
     dev = torch.device(device)
     lock = threading.Lock()
-    # the day descriptors do not depend on the seed: plan the scenario once, replay it per member
-    planner = simulation.make_context(variables, age_counts=age_counts, seed=seeds[0], device=device,
-                                      interventions=interventions, ipc=ipc)
-    plan = planner.make_plan(days)
-    pending = None
-    if summary is not None:
-        from . import summary as _summ
-        pending = _summ.Pending(summary, planner, plan['start_day'])
-    del planner
 
-    def work(k):
+    def work(seed):
         torch.cuda.set_device(dev)
         stream = torch.cuda.Stream(device=dev)
         with torch.cuda.stream(stream):
             with lock:  # context construction touches shared Python state (allocator, caches)
-                ctx = simulation.make_context(variables, age_counts=age_counts, seed=seeds[k], device=device,
-                                              interventions=interventions, ipc=ipc)
+                ctx = setup.context(variables, seed)
             hist = ctx.run_plan(plan)
             stream.synchronize()
-        out[k] = hist
-        del ctx
-        return k
+        return hist
 
-    for start in range(0, len(seeds), concurrent):
-        batch = range(start, min(len(seeds), start + concurrent))
-        with ThreadPoolExecutor(max_workers=min(threads, len(batch))) as pool:
-            list(pool.map(work, batch))
-    if pending is not None:
-        pending.add(np.stack(out))
-        return pending.finish(members=seeds)
-    return np.stack(out)
+    with ThreadPoolExecutor(max_workers=min(threads, len(seeds))) as pool:
+        return np.stack(list(pool.map(work, seeds)))
 
 
 def run_policy_ensemble(variables, seeds, days, policy, age_counts=None, device='cuda:0', engine_factory=None, ipc='auto',
@@ -264,20 +312,15 @@ def run_policy_ensemble(variables, seeds, days, policy, age_counts=None, device=
     as ONE engine group.  Returns (history[K, days, COUNTER_WORDS], levels[K, days], contexts).  An engine library without the
     policy entry points runs the members one after the other by policy.run_host_driven.  `summary` (summary.SummarySpec): the
     EnsembleSummary in place of the history."""
-    from . import policy as _pol
     seeds = list(seeds)
-    mk = lambda sd: simulation.make_context(variables, age_counts=age_counts, seed=sd, device=device, interventions=interventions,
-                                            engine_factory=engine_factory, ipc=ipc)
-    ctxs = [mk(sd) for sd in seeds]
+    setup = Setup(age_counts, device, engine_factory, interventions, ipc)
+    ctxs = setup.members(variables, seeds)   # (ahead of the planner: what the members' library can do decides whether there is one)
     if ctxs[0].engine.policy_f is None:
         hist = np.stack([_pol.run_host_driven(c, policy, days) for c in ctxs])
         if summary is not None:
-            from . import summary as _summ
             hist = _summ.summarise(hist, ctxs[0].nr_ages, summary, ctx=ctxs[0], members=seeds)
     else:
-        planner = mk(seeds[0])
-        plan = planner.make_plan(days, policy=policy)
-        del planner
+        plan = setup.planner(variables, seeds[0]).make_plan(days, policy=policy)
         hist = run_group_plan(ctxs, plan, policy=policy, summary=summary)
     return hist, np.stack([c.policy_levels for c in ctxs]), ctxs
 
@@ -293,42 +336,22 @@ def run_branches(snap, variables, seeds, days, member_variables=None, age_counts
     contexts[m].policy_levels); not together with member_variables.
     Returns (history[K, days, COUNTER_WORDS], contexts); with `summary` (summary.SummarySpec) the EnsembleSummary of the futures
     in place of the history."""
-    from . import engine as _eng
-    from . import snapshot as _snap
     if policy is not None and member_variables is not None:
         raise ValueError('run_branches: a policy and member_variables cannot be combined')
     vs = list(member_variables) if member_variables is not None else [variables] * len(seeds)
     if len(vs) != len(seeds):
         raise ValueError('run_branches: one member_variables entry per seed')
+    setup = Setup(age_counts, device, engine_factory, interventions, None, snapshot=snap)
     plans = []
-    for v, sd in zip(vs, seeds):
-        if plans and v is vs[0]:
-            plans.append(plans[0])
-            continue
-        planner = simulation.make_context(v, age_counts=age_counts, seed=sd, device=device, engine_factory=engine_factory,
-                                          interventions=interventions)
-        planner.restore(snap, engine_state=False)
-        if policy is not None:
-            planner._packed_tables_for_restore(snap.state)   # (the mask shares of the snapshot's last upload: level tables start from them)
-        plans.append(planner.make_plan(days, policy=policy))
-        del planner
-    for k, p in enumerate(plans[1:], 1):
-        if p is not plans[0] and not _same_day_descriptors(plans[0], p):
-            raise ValueError('branch %d differs from branch 0 in more than the values of its mobility / mask '
-                             'interventions: it cannot share a group' % k)
-    ctxs = []
-    for v, sd in zip(vs, seeds):
-        c = simulation.make_context(v, age_counts=age_counts, seed=sd, device=device, engine_factory=engine_factory,
-                                   interventions=interventions)
-        c.restore(snap, engine_state=False)   # (host state and checks; the engines all at once below)
-        ctxs.append(c)
-    group = _eng.EngineGroup([c.engine for c in ctxs])
+    for v, sd in zip(vs, seeds):   # (one planner per distinct variables)
+        plans.append(plans[0] if plans and v is vs[0] else setup.planner(v, sd, policy).make_plan(days, policy=policy))
+    check_shared_days(plans, 'branch')
+    ctxs = setup.members(None, seeds, vs)
+    group, _ = group_for(ctxs)
     try:
-        _snap.unpack_group(group, ctxs[0]._disease, snap.image)
-        for c in ctxs:
-            c.engine.upload_contact_tables(*c._packed_tables_for_restore(snap.state))
-        member_plans = plans if member_variables is not None else None
-        hist = run_group_plan(ctxs, plans[0], member_plans=member_plans, group=group, policy=policy, summary=summary)
+        setup.restore_group(group, ctxs)
+        hist = run_group_plan(ctxs, plans[0], member_plans=plans if member_variables is not None else None, group=group,
+                              policy=policy, summary=summary)
     finally:
         group.close()
     return hist, ctxs
@@ -338,7 +361,6 @@ def transmission_reports(contexts, age_groups=None, group=None):
     """Context.transmission_report of every context, between the same two days: the members' reports as ONE launch per pass on
     the device (reina_group_tx_report), one report per member for host-memory engines.  `group`: an engine.EngineGroup of
     exactly these contexts' engines (stays open); otherwise one is made for the call and closed after it."""
-    from . import engine as _eng, transmission as _tx
     contexts = list(contexts)
     for c in contexts:
         c._check_tx_capable()
@@ -346,11 +368,7 @@ def transmission_reports(contexts, age_groups=None, group=None):
     if not _eng.is_device(contexts[0].engine):
         reps = [_tx.report_engine(c.engine, table, len(labels)) for c in contexts]
     else:
-        own_group = group is None
-        if own_group:
-            group = _eng.EngineGroup([c.engine for c in contexts])
-        elif [e._h.value for e in group.engines] != [c.engine._h.value for c in contexts]:
-            raise ValueError('transmission_reports: `group` is not the group of these contexts')
+        group, own_group = group_for(contexts, group, 'transmission_reports')
         try:
             reps = _tx.report_group(group, table, len(labels))
         finally:

@@ -561,8 +561,7 @@ def particle_filter(variables, n_particles, observations=None, obs_model=None, w
     library without the entry points raises EngineError.  Returns a FilterResult.  Sharded Contexts, K < 2, unknown streams and observations with no date inside the horizon are refused
     (ValueError; `comm`, a sharded population's communicator, is accepted only to be refused the same way); a failing
     member raises SimulationFailed."""
-    from . import ensemble, simulation
-    from . import snapshot as _snap
+    from . import ensemble
     K = int(n_particles)
     if comm is not None:
         raise ValueError('particle_filter: sharded Contexts are not filtered')
@@ -581,17 +580,13 @@ def particle_filter(variables, n_particles, observations=None, obs_model=None, w
         model = obs_model if obs_model is not None else ObservationModel()
         if not isinstance(model, ObservationModel):
             model = ObservationModel(dict(model))
-    ipc = None if snapshot is not None else 'auto'
-    mk = lambda sd: simulation.make_context(variables, age_counts=age_counts, seed=sd, device=device,
-                                            engine_factory=engine_factory, ipc=ipc)
-    planner = mk(seeds[0])
+    setup = ensemble.Setup(age_counts, device, engine_factory, None, None if snapshot is not None else 'auto', snapshot=snapshot)
+    planner = setup.planner(variables, seeds[0])
     if planner.n_shards != 1 or planner.always_collective:
         raise ValueError('particle_filter: sharded Contexts are not filtered')
     txlog = bool(txlog or course)
     if txlog:
         _rep.entry_points(planner.engine, 'filter_log_f', 'logged-clone', 'reina_filter_log.h')
-    if snapshot is not None:
-        planner.restore(snapshot, engine_state=False)
     start_day = int(planner.day)
     if days is None:
         if observations is not None:
@@ -609,25 +604,18 @@ def particle_filter(variables, n_particles, observations=None, obs_model=None, w
         if not any(len(r) for r, _ in aligned.values()):
             raise ValueError('particle_filter: no observed date inside the horizon (days %d .. %d)' % (start_day, start_day + days - 1))
         scorer = _Scorer(model, aligned, K)
-    ctxs = [mk(sd) for sd in seeds]
-    if snapshot is not None:
-        for c in ctxs:
-            c.restore(snapshot, engine_state=False)
-    group = _eng.EngineGroup([c.engine for c in ctxs])
+    ctxs = setup.members(variables, seeds)
+    group, _ = ensemble.group_for(ctxs)
     res = FilterResult(planner, ctxs, group, start_day, planner.start_date, filter_seed)
     rng = np.random.Generator(np.random.PCG64(filter_seed))
     try:
-        if snapshot is not None:
-            _snap.unpack_group(group, ctxs[0]._disease, snapshot.image)
-            for c in ctxs:
-                c.engine.upload_contact_tables(*c._packed_tables_for_restore(snapshot.state))
+        setup.restore_group(group, ctxs)
         day = start_day
         while day < start_day + days:
             n = min(window, start_day + days - day)
             t0 = time.perf_counter()
             plan = planner.make_plan(n)
-            hist = ensemble.run_group_plan(ctxs, plan, group=group, txlog=txlog, course=course) if txlog else \
-                ensemble.run_group_plan(ctxs, plan, group=group)
+            hist = ensemble.run_group_plan(ctxs, plan, group=group, txlog=txlog, course=course)
             t1 = time.perf_counter()
             ll = scorer.score(hist, day) if scorer is not None else np.zeros(K)
             t2 = time.perf_counter()
@@ -644,10 +632,7 @@ def particle_filter(variables, n_particles, observations=None, obs_model=None, w
                     scorer.permute(anc)
             t3 = time.perf_counter()
             if pairs:
-                if txlog:
-                    clone_group(group, pairs, log=ctxs[0].transmission_log.device)
-                else:
-                    clone_group(group, pairs)
+                clone_group(group, pairs, log=ctxs[0].transmission_log.device if txlog else None)
             t4 = time.perf_counter()
             res.windows.append(dict(start_day=day, days=n, loglik=ll, ess=e, ancestors=anc, resampled=resampled,
                                     history=hist, observed=scorer is not None))

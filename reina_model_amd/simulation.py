@@ -324,29 +324,20 @@ def run_monte_carlo(scenario_name, seeds=range(1000), device='cuda:0', group_siz
     days = v['simulation_days'] if days is None else days
     seeds = list(seeds)
     dfs = []
-    pending = None
-    for start in range(0, len(seeds), group_size):
-        part = seeds[start:start + group_size]
-        planner = make_context(v, age_counts=age_counts, seed=part[0], device=device, engine_factory=engine_factory, ipc=ipc)
-        plan = planner.make_plan(days)
-        members = [make_context(v, age_counts=age_counts, seed=sd, device=device, engine_factory=engine_factory, ipc=ipc)
-                   for sd in part]
-        if summary is not None:
-            if pending is None:
-                from . import summary as _summ
-                pending = _summ.Pending(summary, planner, plan['start_day'])
-            ensemble.run_group_plan(members, plan, summary=pending)
-            del members, planner
-            continue
+    # (ensemble.Setup / plan_once: ONE planner and one plan for all chunks -- the plan does not depend on the seed)
+    setup = ensemble.Setup(age_counts, device, engine_factory, None, ipc)
+    plan, pending = ensemble.plan_once(setup, v, seeds[0], days, summary)
+    for part in ensemble.chunks(seeds, group_size):
+        members = setup.members(v, part)
         t0 = time.perf_counter()
-        hist = ensemble.run_group_plan(members, plan)
+        hist = ensemble.run_group_plan(members, plan, summary=pending)
         ms_per_day = (time.perf_counter() - t0) * 1000 / days / len(part)
-        for m, sd in enumerate(part):
+        for m, sd in enumerate(part if summary is None else ()):
             df, _ = _frames_from_history(members[m], hist[m], plan['mobility_history'],
                                          date.fromisoformat(v['start_date']), ms_per_day, want_adf=False)
             df['run'] = sd
             dfs.append(df)
-        del members, planner
+        del members
     if summary is not None:
         out = pending.finish(members=seeds)
         if write_csv:

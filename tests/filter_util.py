@@ -65,18 +65,16 @@ def continuation(v, ages, seeds, a, m, cut, days, engine_factory=None, device='c
     """Run a group of `seeds` for `cut` days, clone member a into member m, run `days` more as a group.  Returns (member m's
     history of the last `days` days, its Context, the history and Context of a restore of a snapshot of seeds[a]'s run at
     `cut` into a fresh Context with seed seeds[m], run `days` days alone)."""
-    mk = lambda sd, ipc='auto': simulation.make_context(v, age_counts=ages, seed=sd, device=device, engine_factory=engine_factory,
-                                                        ipc=ipc)
-    planner = mk(seeds[0])
-    ctxs = [mk(sd) for sd in seeds]
-    group = eng.EngineGroup([c.engine for c in ctxs])
+    setup = ensemble.Setup(ages, device, engine_factory, None, 'auto')
+    planner, ctxs = setup.planner(v, seeds[0]), setup.members(v, seeds)
+    group, _ = ensemble.group_for(ctxs)
     try:
         ensemble.run_group_plan(ctxs, planner.make_plan(cut), group=group)
         filtering.clone_group(group, [(m, a)])
         hist = ensemble.run_group_plan(ctxs, planner.make_plan(days), group=group)
     finally:
         group.close()
-    solo = mk(seeds[a])
+    solo = setup.context(v, seeds[a])
     solo.run(cut)
     snap = solo.snapshot()
     ref = simulation.make_context(v, age_counts=ages, seed=seeds[m], device=device, engine_factory=engine_factory, snapshot=snap)

@@ -215,9 +215,9 @@ def test_no_observations_is_run_group_plan():
     r = _pf(v, ages, 3, None, days=30, seeds=seeds, window=7)
     assert all(not w['resampled'] for w in r.windows) and r.log_evidence == 0.0
     assert [w['days'] for w in r.windows] == [7, 7, 7, 7, 2]
-    planner = simulation.make_context(v, age_counts=ages, seed=seeds[0], ipc='auto', engine_factory=PAR)
-    ctxs = [simulation.make_context(v, age_counts=ages, seed=s, ipc='auto', engine_factory=PAR) for s in seeds]
-    want = ensemble.run_group_plan(ctxs, planner.make_plan(30))
+    setup = ensemble.Setup(ages, engine_factory=PAR, ipc='auto')
+    ctxs = setup.members(v, seeds)
+    want = ensemble.run_group_plan(ctxs, setup.planner(v, seeds[0]).make_plan(30))
     assert np.array_equal(r.paths(), want)
     for c, w in zip(r.contexts, ctxs):
         assert np.array_equal(c.engine.read_counters(), w.engine.read_counters())

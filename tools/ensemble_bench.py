@@ -10,11 +10,10 @@ ages = datasets.get_population_for_area()
 N = int(ages.sum()); days = 365
 ensemble.run_ensemble(v, [999, 998], 60, age_counts=ages)  # warm up
 # step time alone (members built beforehand): the launch-count argument for groups
-from reina_model_amd import simulation
+setup = ensemble.Setup(ages)
 for members in (1, 8, 32, 64):
-    planner = simulation.make_context(v, age_counts=ages, seed=0)
-    plan = planner.make_plan(days)
-    ctxs = [simulation.make_context(v, age_counts=ages, seed=s) for s in range(members)]
+    plan = setup.planner(v, 0).make_plan(days)
+    ctxs = setup.members(v, range(members))
     torch.cuda.synchronize(); t0 = time.perf_counter()
     ensemble.run_group_plan(ctxs, plan)
     torch.cuda.synchronize(); dt = time.perf_counter() - t0

@@ -37,7 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (a worker of --logged imports the package of the tree it is told: --root DIR)
 sys.path.insert(0, os.path.abspath(sys.argv[sys.argv.index('--root') + 1]) if '--root' in sys.argv[:-1] else ROOT)
 
-from reina_model_amd import datasets, engine as eng, ensemble, filtering, simulation, snapshot as snapmod  # noqa: E402
+from reina_model_amd import datasets, engine as eng, ensemble, filtering, snapshot as snapmod  # noqa: E402
 from reina_model_amd.variables import VARIABLE_DEFAULTS  # noqa: E402
 
 PEAK = 6.3e12
@@ -274,9 +274,9 @@ def case_logged(K, windows_cap, reps, parent, rounds, on_round=None):
 def case_1e7(n, K, days, reps):
     v = copy.deepcopy(VARIABLE_DEFAULTS)
     ages = datasets.scaled_population(n)
-    planner = simulation.make_context(v, age_counts=ages, seed=1, ipc='auto')
-    ctxs = [simulation.make_context(v, age_counts=ages, seed=100 + k, ipc='auto') for k in range(K)]
-    group = eng.EngineGroup([c.engine for c in ctxs])
+    setup = ensemble.Setup(ages, ipc='auto')
+    planner, ctxs = setup.planner(v, 1), setup.members(v, range(100, 100 + K))
+    group, _ = ensemble.group_for(ctxs)
     try:
         t0 = time.perf_counter()
         ensemble.run_group_plan(ctxs, planner.make_plan(days), record_history=False, group=group)
