@@ -369,6 +369,14 @@ class CourseLog:
         """CourseReport of the days [0, n_days) (default: the days run so far)"""
         return _rep.report_of(COURSE, self, age_groups, n_days)
 
+    def detection_report(self, age_groups=None, n_days=None):
+        """detection.DetectionReport of the days [0, n_days) (default: the days run so far): ascertainment by age, severity and
+        date of infection, transmission from agents never detected and before a detection, lead times, and what tracing adds.
+        One launch where the course is a single engine's on the device and the library has the entry points,
+        detection.report_numpy on host copies otherwise.  Reads the engine's state, the log and the course only."""
+        from . import detection as _det
+        return _det.report_course(self, age_groups, n_days)
+
 
 def run_host_driven(ctx, days, record_history=True, on_day=None):
     """txlog.run_host_driven with the course kept beside the log: per day iterate(), read the hot words back, record both --

@@ -1360,6 +1360,9 @@ int reina_profile_read(reina_engine_t *e, double *scan_ms_total, uint64_t *scan_
 // the clinical course log attached to a transmission log (include/reina_course.h): kernels and entry points
 #include "k_course.inc"
 
+// the detection report taken of a course log and its transmission log (include/reina_detection.h): kernel and entry point
+#include "k_detection.inc"
+
 // the vaccination report taken of a transmission log (include/reina_vaccination.h): kernel and entry point
 #include "k_vaccination.inc"
 

@@ -381,9 +381,11 @@ class Handle:
 
     def close(self):
         if self._h:
+            # (the handle is reset first and from its own type: at interpreter shutdown this module's globals may be None
+            # already, and a handle left set behind a destroy that ran would be destroyed a second time by __del__)
+            h, self._h = self._h, type(self._h)()
             self._closing()
-            self.f[self.DESTROY](self._h)
-            self._h = ctypes.c_void_p()
+            self.f[self.DESTROY](h)
 
     def __del__(self):
         try:
@@ -400,14 +402,15 @@ class Engine(Handle):
         self.f = bind_abi(lib, prefix)
         self.alloc = allocator
         # the headers beside reina_hip.h (snapshots, transmission-tree reports, the particle filter's in-group clone, triggered
-        # interventions, the dated transmission log, the clone of a logged group, lineage reports, the clinical course log, the vaccination report, ensemble summaries): each bound when the library has it,
+        # interventions, the dated transmission log, the clone of a logged group, lineage reports, the clinical course log, the vaccination report, the detection report, ensemble summaries): each bound when the library has it,
         # None otherwise
-        from . import course, filtering, lineage, policy, snapshot, summary, transmission, txlog, vaccination
+        from . import course, detection, filtering, lineage, policy, snapshot, summary, transmission, txlog, vaccination
         for attr, bind in (('snap_f', snapshot.bind_snapshot_abi), ('tx_f', transmission.bind_tx_abi),
                            ('filter_f', filtering.bind_filter_abi), ('filter_log_f', filtering.bind_filter_log_abi),
                            ('policy_f', policy.bind_policy_abi),
                            ('txlog_f', txlog.bind_txlog_abi), ('lineage_f', lineage.bind_lineage_abi),
                            ('course_f', course.bind_course_abi), ('vacc_f', vaccination.bind_vacc_abi),
+                           ('detect_f', detection.bind_detect_abi),
                            ('summary_f', summary.bind_summary_abi)):
             setattr(self, attr, bind(lib, prefix))
         self.config = config

@@ -24,7 +24,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import (course as _crs, engine as _eng, lineage as _lin, policy as _pol, reports as _rep, simulation, snapshot as _snap,
+from . import (course as _crs, detection as _det, engine as _eng, lineage as _lin, policy as _pol, reports as _rep, simulation, snapshot as _snap,
                summary as _summ, transmission as _tx, txlog as _txl, vaccination as _vac)
 from .dayrun import History, replay_plan
 from .filtering import particle_filter  # noqa: F401  (conditioned ensembles: reina_model_amd/filtering.py)
@@ -401,3 +401,8 @@ def course_reports(contexts, age_groups=None, n_days=None):
 def vaccination_reports(contexts, age_groups=None, n_days=None):
     """vaccination.VaccinationReport of every context (one launch: reina_vacc_report)"""
     return _rep.reports_of_contexts(_vac.VACCINATION, contexts, age_groups, n_days)
+
+
+def detection_reports(contexts, age_groups=None, n_days=None):
+    """detection.DetectionReport of every context (one launch: reina_detect_report); the contexts keep course logs"""
+    return _rep.reports_of_contexts(_det.DETECTION, contexts, age_groups, n_days)

@@ -488,6 +488,12 @@ class FilterResult:
         from .vaccination import VACCINATION
         return self._reports(VACCINATION, age_groups, n_days)
 
+    def detection_reports(self, age_groups=None, n_days=None):
+        """detection.DetectionReport of every final particle by one launch (ensemble.detection_reports); needs course=True.  A
+        clone carries the cold records, the log and the course, so a particle's links and detections are its ancestral path's"""
+        from .detection import DETECTION
+        return self._reports(DETECTION, age_groups, n_days)
+
     def _band_frame(self, values, q, index, means=()):
         import pandas as pd
         q = [float(x) for x in np.atleast_1d(q)]

@@ -3,7 +3,7 @@ csrc/k_addons.inc.  One classification of the links, one age lookup, one forest,
 rule, one device call, one guard for missing entry points and one base for the Report classes -- so that the three
 specifications agree by construction on what a root, a link and a bad link are, as the three kernels do.
 
-And how a report of a log is TAKEN (txlog.py, lineage.py, course.py, vaccination.py): each of those modules declares a Kind,
+And how a report of a log is TAKEN (txlog.py, lineage.py, course.py, vaccination.py, detection.py): each of those modules declares a Kind,
 and the three routes -- of one log (report_of), of the members of a log on the device (reports_of_device), of a list of
 Contexts (reports_of_contexts) -- and the rule of which group log a list of Contexts shares (group_log, shared_log) are
 written here once.
@@ -170,7 +170,7 @@ def device_words(engine, f, name, head, members, words, scratch_bytes=None, stal
 # ------------------------------------------------------------------------------------------------ taking a report of a log
 
 # What is particular to one report taken of a log; its module declares one (txlog.LOG, lineage.LINEAGE, course.COURSE,
-# vaccination.VACCINATION) and binds its public names onto the three routes below.
+# vaccination.VACCINATION, detection.DETECTION) and binds its public names onto the three routes below.
 #   name         the report's name in refusals ('log_reports')
 #   of           what it is taken of: the Context attribute that holds the log ('transmission_log' or 'course_log')
 #   arguments    (ctx, *args) -> (table, labels, *params): the Context's report groups and the report's own parameters, checked
