@@ -29,7 +29,15 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
     return x;
 }
 
-// +1 in LDS histogram cell b of every lane with b >= 0; the lanes that share the first such lane's cell add once.
+// +1 in an LDS cell that is the same for every lane (a scalar of a report), of every lane with p: one ballot, one popcount and
+// one atomic by lane 0 where the count is not zero
+__device__ __forceinline__ void wave_tally(uint32_t *cell, bool p) {
+    const uint32_t n = (uint32_t)__popcll(__ballot(p));
+    if ((threadIdx.x & 63u) == 0u && n) atomicAdd(cell, n);
+}
+
+// +1 in LDS histogram cell b of every lane with b >= 0, for cells that differ by lane (one cell for all: wave_tally, which needs
+// neither the shuffle nor the second ballot); the lanes that share the first such lane's cell add once.
 // (A ballot and a popcount: not wave_add with val = 1, whose butterfly costs twelve shuffles.)
 __device__ __forceinline__ void wave_count(uint32_t *hist, int b) {
     const uint64_t act = __ballot(b >= 0);
@@ -71,6 +79,38 @@ __device__ __forceinline__ void flush_lds(const T *lds, uint32_t n, GAS unsigned
         if (lds[k]) atomicAdd(&dst[k], (unsigned long long)lds[k]);
 }
 
+// this launch's member's block of an array of `words_a_member` elements a member (log words, course records, report blocks):
+// the blockIdx.y-th of a group's, the only one of an engine's
+template <bool GROUP, class T>
+__device__ __forceinline__ GAS T *member_block(T *p, size_t words_a_member) {
+    return (GAS T *)p + (GROUP ? (size_t)blockIdx.y * words_a_member : 0u);
+}
+
+// a thread's two agents of tile t, t * REPORT_TILE + j * REPORT_THREADS + threadIdx.x, and their hot words (0 beyond the population)
+__device__ __forceinline__ void tile_words(uint32_t t, uint32_t N, const GAS uint32_t *hot, uint32_t (&idx)[2], uint32_t (&w)[2]) {
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        idx[j] = t * REPORT_TILE + (uint32_t)j * REPORT_THREADS + threadIdx.x;
+        w[j] = idx[j] < N ? hot[idx[j]] : 0u;
+    }
+}
+
+// A wave's walk over tile t of the ACTIVE bit plane, in the 512-agent tiles of 16 plane words that k_day's sparse stream uses
+// (the plane holds whole tiles: REINA_BITS_WORDS).  Lane l looks at agent t * REPORT_TILE + 64 j + l in round j -- bit l & 31 of
+// plane word 2 j + (l >> 5), which lane 2 j + (l >> 5) holds -- so the hot words of a dense tile are fetched coalesced.
+// false: no bit of the tile is set.  Otherwise w[j] is the hot word of round j's agent where its bit is set, 0 where it is not.
+__device__ __forceinline__ bool active_tile(const GAS uint32_t *plane, const GAS uint32_t *hot, uint32_t t, uint32_t N, uint32_t lane, uint32_t (&w)[8]) {
+    const uint32_t wd = plane[t * 16u + (lane & 15u)];
+    if (!__ballot(wd != 0u)) return false;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint32_t bits = (uint32_t)__shfl((int)wd, 2 * j + (int)(lane >> 5));
+        const uint32_t i = t * REPORT_TILE + (uint32_t)j * 64u + lane;
+        w[j] = ((bits >> (lane & 31u)) & 1u) && i < N ? hot[i] : 0u;
+    }
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------
 // the population by age group, as the reports' kernels take it
 
@@ -79,6 +119,27 @@ struct AgeGroupArgs {
     int32_t age_start[REINA_MAX_AGES + 1];
     uint8_t group[REINA_MAX_AGES];
 };
+
+// ... and as a report kernel keeps it in LDS: declared __shared__, loaded by the whole workgroup ahead of its __syncthreads().
+// 644 bytes: age_of never looks at the closing entry of age_start (its `mid` stays at or below the top age), so the top age has
+// that word.
+struct ReportAges {
+    int32_t start[REINA_MAX_AGES];
+    int32_t top;
+    uint8_t group[REINA_MAX_AGES];
+    __device__ __forceinline__ void load(const AgeGroupArgs &p) {
+        static_assert(REPORT_THREADS > REINA_MAX_AGES, "one thread an age, and one for the top");
+        const uint32_t tid = threadIdx.x;
+        if (tid < REINA_MAX_AGES) {
+            start[tid] = p.age_start[tid];
+            group[tid] = p.group[tid];
+        }
+        if (tid == REINA_MAX_AGES) top = (int32_t)p.nr_ages - 1;
+    }
+    __device__ __forceinline__ int age_of(uint32_t agent) const { return ::age_of(start, agent, 0, top); }
+    __device__ __forceinline__ int group_of(uint32_t agent) const { return (int)group[age_of(agent)]; }
+};
+static_assert(sizeof(ReportAges) == (REINA_MAX_AGES + 1) * 4u + REINA_MAX_AGES, "the two tables and not a byte more");
 
 static int age_group_args(const reina_engine_t *e, const uint8_t *age_group, uint32_t n_groups, uint32_t max_groups, const char *what, AgeGroupArgs *a) {
     if (!age_group || n_groups < 1u || n_groups > max_groups)
@@ -97,8 +158,8 @@ static int age_group_args(const reina_engine_t *e, const uint8_t *age_group, uin
 // ---------------------------------------------------------------------------------------------
 // the links of a tile: what an agent's record says of its infection, classified once for the tree report and the dated log
 
-struct Links {               // a thread's two agents of a tile: tile * REPORT_TILE + j * REPORT_THREADS + threadIdx.x
-    uint32_t idx[2], w[2];   // the agent and its hot word (0 beyond the population)
+struct Links {               // a thread's two agents of a tile
+    uint32_t idx[2], w[2];   // the agent and its hot word (tile_words)
     bool inf[2];             // ever infected: nothing below is set of an agent that was not
     int32_t src[2];          // the cold record's infector (-1: none) ...
     uint32_t n[2];           // ... and n_infected
@@ -115,10 +176,9 @@ template <bool LOG>
 __device__ __forceinline__ bool load_links(Links &k, uint32_t tile, uint32_t N, const GAS uint32_t *hot, const GAS reina_cold_t *cold,
                                            const GAS uint32_t *log, uint32_t *cnt, int at_inf, int at_root, int at_linked, int at_bad) {
     k = Links();
+    tile_words(tile, N, hot, k.idx, k.w);
 #pragma unroll
     for (int j = 0; j < 2; j++) {
-        k.idx[j] = tile * REPORT_TILE + (uint32_t)j * REPORT_THREADS + threadIdx.x;
-        k.w[j] = k.idx[j] < N ? hot[k.idx[j]] : 0u;
         k.lw[j] = LOG && k.idx[j] < N ? log[k.idx[j]] : 0u;
         k.inf[j] = RH_STATE(k.w[j]) != RS_SUSCEPTIBLE;
         k.src[j] = -1;
@@ -138,6 +198,7 @@ __device__ __forceinline__ bool load_links(Links &k, uint32_t tile, uint32_t N, 
             k.sw[j] = hot[k.src[j]];
             if (LOG) k.sl[j] = log[k.src[j]];
         }
+    // (not wave_tally: the counts of a thread's two agents are summed first, four LDS atomics a tile where it would take eight)
     uint32_t c[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int j = 0; j < 2; j++) {
@@ -234,9 +295,12 @@ static int engine_run_days(reina_engine_t *e0, const reina_day_t *days, uint32_t
 
 // ---------------------------------------------------------------------------------------------
 // what the entry points of the attachments share on the host.  A new attachment is expected to refuse through refuse and to
-// stage what it uploads through a StageRing (k_common.inc), to take the front end of a flat report by day from day_report and
-// its members' words to and from the host from member_copy; forest_passes and the member table (member_table,
-// with_member_table) are for reports that resolve the transmission forest by pointer jumping.
+// stage what it uploads through a StageRing (k_common.inc), to take a flat report by day from front to launch through day_report
+// and its members' words to and from the host from member_copy; forest_passes and the member table (member_table,
+// with_member_table) are for reports that resolve the transmission forest by pointer jumping.  Its kernels are expected to find
+// their member's blocks with member_block, to keep the age tables in a ReportAges, to walk the ACTIVE plane with active_tile or
+// the tiles with tile_words (load_links where they need the links), to count a scalar with wave_tally -- out_of_range one
+// predicate a date -- and a histogram with wave_count, to add to the tables by day with wave_add and to flush with flush_lds.
 
 // a member's n_agents elements of `elem` bytes at member * stride of `base`, to the host or from it; waits for the stream
 static int member_copy(const attachment *a, void *base, size_t stride, size_t elem, uint32_t member, void *host, bool to_host, const char *what, hipStream_t s) {
@@ -257,19 +321,24 @@ struct TxlArgs {
     uint32_t n_days;
 };
 
-// The front end of such a report: the age groups, n_days and the buffer checked in that order under the prefix `what`, the
-// members' blocks of words(n_days) 64-bit words cleared, `a` filled, and the grid of the one launch: four workgroups a compute
-// unit over the tiles (each flushes its LDS tables once).
-static int day_report(const attachment *l, const char *what, uint32_t max_groups, size_t (*words)(uint32_t n_days), const uint8_t *age_group,
-                      uint32_t n_groups, uint32_t n_days, uint64_t *dev_report, hipStream_t s, TxlArgs *a, uint32_t *grid) {
-    if (int rc = age_group_args(l->e0, age_group, n_groups, max_groups, what, &a->p)) return rc;
-    a->n_days = n_days;
+// Such a report from front to launch: the age groups, n_days and the buffer checked in that order under the prefix `what`, the
+// members' blocks of `words` 64-bit words (the header's REINA_*_REPORT_WORDS(n_days)) cleared, then launch(a, grid, K) with the
+// kernel's arguments filled and the grid of the one launch: four workgroups a compute unit over the tiles (each flushes its LDS
+// tables once).  The launch is the caller's callable, not a parameter: launch_members has to name KERNEL<true> and
+// KERNEL<false>, and a callable also has room for what a report queues between the clearing and its kernel.
+template <class Launch>
+static int day_report(const attachment *l, const char *what, uint32_t max_groups, size_t words, const uint8_t *age_group, uint32_t n_groups, uint32_t n_days,
+                      uint64_t *dev_report, hipStream_t s, Launch launch) {
+    TxlArgs a;
+    uint32_t grid;
+    if (int rc = age_group_args(l->e0, age_group, n_groups, max_groups, what, &a.p)) return rc;
+    a.n_days = n_days;
     if (n_days < 1u || n_days > REINA_MAX_DAYS) return refuse(std::string(what) + ": n_days must be in [1, REINA_MAX_DAYS]");
     if (!dev_report || (reinterpret_cast<uintptr_t>(dev_report) & 15u)) return refuse(std::string(what) + ": the report must be a 16-byte aligned device buffer");
     const uint32_t K = (uint32_t)l->members.size();
-    HIP_CHECK(hipMemsetAsync(dev_report, 0, words(n_days) * 8u * K, s));
-    *grid = member_grid(l->e0->n_cus, K, (a->p.n_agents + REPORT_TILE - 1u) / REPORT_TILE, 4u);
-    return REINA_OK;
+    HIP_CHECK(hipMemsetAsync(dev_report, 0, words * 8u * K, s));
+    grid = member_grid(l->e0->n_cus, K, (a.p.n_agents + REPORT_TILE - 1u) / REPORT_TILE, 4u);
+    return launch(a, grid, K);
 }
 
 // the passes of a forest report (the tree report's, the lineage report's): links, `rounds` of pointer jumping, a tally, a

@@ -4,8 +4,8 @@
 //
 // Three kernels, each bound by memory traffic:
 //   k_course_begin   streams the hot words (16 bytes a lane) and writes every record (32 bytes a lane).
-//   k_course_day     takes k_txlog_day's place in the log's launch of the day when a course is attached: the same 512-agent
-//                    tiles of the ACTIVE plane, one tile a wave, the same update of the log word (txl_day_update, in both
+//   k_course_day     takes k_txlog_day's place in the log's launch of the day when a course is attached: the same walk over
+//                    the ACTIVE plane (active_tile), one tile a wave, the same update of the log word (txl_day_update, in both
 //                    forms), and for the active agents in a state >= ILLNESS or with RH_DETECTED one 8-byte load of the record
 //                    and a store where it changes.  An incubating undetected agent costs nothing beyond k_txlog_day.  The
 //                    ACTIVE plane is enough: a record closes with its outcome, and k_scan clears RH_ACTIVE on the day AFTER a
@@ -17,14 +17,13 @@
 // One lane owns an agent: no atomics on the records, no fences (a kernel boundary lies on either side of every launch).
 #include "../../include/reina_course.h"
 
-#define CRS_THREADS REPORT_THREADS
-#define CRS_TILE REPORT_TILE
 #define CRS_HIST (REINA_COURSE_DELAY_SUM - REINA_COURSE_DELAY)                            // delay and delay_n, as the block has them
 #define CRS_SUMS (REINA_COURSE_PATHWAY - REINA_COURSE_DELAY_SUM)
 #define CRS_TAIL (REINA_COURSE_FIXED_WORDS - REINA_COURSE_PATHWAY)                        // pathway and the scalars
 static_assert(REINA_COURSE_FIXED_WORDS == 8624u && REINA_COURSE_DAY_WORDS == 144u, "report layout");
 static_assert(REINA_COURSE_MAX_GROUPS == REINA_TXLOG_MAX_GROUPS, "the groups are the log report's");
-static_assert(CRS_HIST * 4u + CRS_SUMS * 8u + CRS_TAIL * 4u + (REINA_MAX_AGES + 1) * 4u + REINA_MAX_AGES <= 40u * 1024u, "LDS budget of k_course_report");
+static_assert(REINA_COURSE_S_WITH_OUTCOME == REINA_COURSE_S_WITH_DETECTION + 3, "the with_* scalars stand in the order of the record's fields");
+static_assert(CRS_HIST * 4u + CRS_SUMS * 8u + CRS_TAIL * 4u + sizeof(ReportAges) <= 40u * 1024u, "LDS budget of k_course_report");
 
 typedef unsigned long long crs_rec;
 #define CRS_FIELD(r, bit) ((uint32_t)((r) >> (bit)) & 0xFFFFu)
@@ -41,12 +40,12 @@ __device__ __forceinline__ crs_rec crs_begin_record(uint32_t w) {
 
 // the records are padded to whole tiles like the log (beyond n_agents: the record of a susceptible agent, never read back)
 template <bool GROUP>
-__global__ __launch_bounds__(CRS_THREADS) void k_course_begin(const MemberRef *M_, const MemberRef one_, crs_rec *rec, size_t stride, uint32_t N) {
+__global__ __launch_bounds__(REPORT_THREADS) void k_course_begin(const MemberRef *M_, const MemberRef one_, crs_rec *rec, size_t stride, uint32_t N) {
     MEMBER_OF_LAUNCH;
     const GAS uint32_t *hot = (const GAS uint32_t *)mref_.B.hot;
-    GAS crs_rec *C = (GAS crs_rec *)rec + (GROUP ? (size_t)blockIdx.y * stride : 0u);
+    GAS crs_rec *C = member_block<GROUP>(rec, stride);
     const uint32_t quads = (N + 3u) / 4u;
-    for (uint32_t q = blockIdx.x * CRS_THREADS + threadIdx.x; q < quads; q += gridDim.x * CRS_THREADS) {
+    for (uint32_t q = blockIdx.x * REPORT_THREADS + threadIdx.x; q < quads; q += gridDim.x * REPORT_THREADS) {
         const uint32_t i = 4u * q;
         v4u_ w;
         if (i + 3u < N) {
@@ -84,36 +83,29 @@ __device__ __forceinline__ void crs_day_update(GAS crs_rec *C, uint32_t i, uint3
 
 // k_txlog_day with the course update beside the log's: four waves a workgroup, one tile a wave and round
 template <bool GROUP>
-__global__ __launch_bounds__(CRS_THREADS) void k_course_day(const MemberRef *M_, const MemberRef one_, uint32_t *log, crs_rec *rec, size_t stride, uint32_t N,
-                                                            uint32_t day, uint32_t by_hot) {
+__global__ __launch_bounds__(REPORT_THREADS) void k_course_day(const MemberRef *M_, const MemberRef one_, uint32_t *log, crs_rec *rec, size_t stride, uint32_t N,
+                                                               uint32_t day, uint32_t by_hot) {
     MEMBER_OF_LAUNCH;
     const GAS uint32_t *hot = (const GAS uint32_t *)mref_.B.hot;
     const GAS uint32_t *plane = (const GAS uint32_t *)mref_.B.active_bits;
-    GAS uint32_t *L = (GAS uint32_t *)log + (GROUP ? (size_t)blockIdx.y * stride : 0u);
-    GAS crs_rec *C = (GAS crs_rec *)rec + (GROUP ? (size_t)blockIdx.y * stride : 0u);
+    GAS uint32_t *L = member_block<GROUP>(log, stride);
+    GAS crs_rec *C = member_block<GROUP>(rec, stride);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t tiles = (N + CRS_TILE - 1u) / CRS_TILE;
+    const uint32_t tiles = (N + REPORT_TILE - 1u) / REPORT_TILE;
     const uint32_t d8 = day & 0xFFu, o8 = (day + 1u) & 0xFFu;
-    for (uint32_t t = blockIdx.x * (CRS_THREADS / 64u) + wave; t < tiles; t += gridDim.x * (CRS_THREADS / 64u)) {
-        const uint32_t wd = plane[t * 16u + (lane & 15u)];   // (the plane holds whole tiles: REINA_BITS_WORDS)
-        if (!__ballot(wd != 0u)) continue;
+    for (uint32_t t = blockIdx.x * (REPORT_THREADS / 64u) + wave; t < tiles; t += gridDim.x * (REPORT_THREADS / 64u)) {
         uint32_t w[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint32_t bits = (uint32_t)__shfl((int)wd, 2 * j + (int)(lane >> 5));
-            const uint32_t i = t * CRS_TILE + (uint32_t)j * 64u + lane;
-            w[j] = ((bits >> (lane & 31u)) & 1u) && i < N ? hot[i] : 0u;
-        }
+        if (!active_tile(plane, hot, t, N, lane, w)) continue;
         // the records of the agents the course looks at, all in flight together (0: a closed record, nothing to do)
         crs_rec r[8];
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-            const uint32_t i = t * CRS_TILE + (uint32_t)j * 64u + lane, st = RH_STATE(w[j]);
+            const uint32_t i = t * REPORT_TILE + (uint32_t)j * 64u + lane, st = RH_STATE(w[j]);
             r[j] = st >= RS_ILLNESS || (st != RS_SUSCEPTIBLE && (w[j] & RH_DETECTED)) ? C[i] : 0ull;
         }
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-            const uint32_t i = t * CRS_TILE + (uint32_t)j * 64u + lane;
+            const uint32_t i = t * REPORT_TILE + (uint32_t)j * 64u + lane;
             if (RH_STATE(w[j]) == RS_SUSCEPTIBLE) continue;
             txl_day_update(L, i, w[j], day, d8, o8, by_hot);
             crs_day_update(C, i, w[j], r[j], day);
@@ -131,38 +123,31 @@ __device__ __forceinline__ void crs_delay(uint32_t *s_h, crs_rec *s_sum, uint32_
 
 // 256 threads, tiles of 512 agents (two per thread), the workgroup's tiles strided over the grid
 template <bool GROUP>
-__global__ __launch_bounds__(CRS_THREADS) void k_course_report(const MemberRef *M_, const MemberRef one_, const uint32_t *log, const crs_rec *rec,
-                                                               size_t stride, uint64_t *report, const TxlArgs a) {
+__global__ __launch_bounds__(REPORT_THREADS) void k_course_report(const MemberRef *M_, const MemberRef one_, const uint32_t *log, const crs_rec *rec,
+                                                                  size_t stride, uint64_t *report, const TxlArgs a) {
     __shared__ uint32_t s_h[CRS_HIST];       // delay, delay_n
     __shared__ crs_rec s_sum[CRS_SUMS];      // delay_sum
     __shared__ uint32_t s_p[CRS_TAIL];       // pathway, scalars
-    __shared__ int32_t s_as[REINA_MAX_AGES + 1];
-    __shared__ uint8_t s_grp[REINA_MAX_AGES];
+    __shared__ ReportAges s_ages;
     MEMBER_OF_LAUNCH;
     const GAS uint32_t *hot = (const GAS uint32_t *)mref_.B.hot;
-    const GAS uint32_t *L = (const GAS uint32_t *)log + (GROUP ? (size_t)blockIdx.y * stride : 0u);
-    const GAS crs_rec *C = (const GAS crs_rec *)rec + (GROUP ? (size_t)blockIdx.y * stride : 0u);
-    GAS unsigned long long *R = (GAS unsigned long long *)report + (GROUP ? (size_t)blockIdx.y * REINA_COURSE_REPORT_WORDS(a.n_days) : 0u);
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    for (uint32_t k = tid; k < CRS_HIST; k += CRS_THREADS) s_h[k] = 0u;
+    const GAS uint32_t *L = member_block<GROUP>(log, stride);
+    const GAS crs_rec *C = member_block<GROUP>(rec, stride);
+    GAS unsigned long long *R = member_block<GROUP>((unsigned long long *)report, REINA_COURSE_REPORT_WORDS(a.n_days));
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t k = tid; k < CRS_HIST; k += REPORT_THREADS) s_h[k] = 0u;
     if (tid < CRS_SUMS) s_sum[tid] = 0ull;
     if (tid < CRS_TAIL) s_p[tid] = 0u;
-    if (tid <= REINA_MAX_AGES) s_as[tid] = a.p.age_start[tid];
-    if (tid < REINA_MAX_AGES) s_grp[tid] = a.p.group[tid];
+    s_ages.load(a.p);
     __syncthreads();
-    const uint32_t N = a.p.n_agents, D = a.n_days, tiles = (N + CRS_TILE - 1u) / CRS_TILE;
-    const int top = (int)a.p.nr_ages - 1;
+    const uint32_t N = a.p.n_agents, D = a.n_days, tiles = (N + REPORT_TILE - 1u) / REPORT_TILE;
     uint32_t *s_sc = s_p + (REINA_COURSE_SCALARS - REINA_COURSE_PATHWAY);
     GAS unsigned long long *day_t[3] = {R + REINA_COURSE_DETECTIONS(D), R + REINA_COURSE_ADMISSIONS(D), R + REINA_COURSE_ICU_ADMISSIONS(D)};
     GAS unsigned long long *dead_t = R + REINA_COURSE_DEATHS(D), *rcv_t = R + REINA_COURSE_RECOVERIES(D), *coh_t = R + REINA_COURSE_COHORT(D);
     for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         uint32_t idx[2], w[2], lw[2];
         crs_rec r[2];
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            idx[j] = t * CRS_TILE + (uint32_t)j * CRS_THREADS + tid;
-            w[j] = idx[j] < N ? hot[idx[j]] : 0u;
-        }
+        tile_words(t, N, hot, idx, w);
         if (!__ballot(RH_STATE(w[0]) != RS_SUSCEPTIBLE || RH_STATE(w[1]) != RS_SUSCEPTIBLE)) continue;
 #pragma unroll
         for (int j = 0; j < 2; j++) {
@@ -181,19 +166,16 @@ __global__ __launch_bounds__(CRS_THREADS) void k_course_report(const MemberRef *
             const bool k[4] = {inf && f[0] < TXL_BEFORE, inf && f[1] < TXL_BEFORE, inf && f[2] < TXL_BEFORE, inf && f[3] < TXL_BEFORE};
             const int det = (int)f[0], adm = (int)f[1], icu = (int)f[2], out = (int)f[3], o = (int)oi;
             int g = 0;
-            if (inf) g = (int)s_grp[age_of(s_as, idx[j], 0, top)];
-            // the scalars: one LDS atomic a wave and kind
-            const uint32_t oor = (k[0] && f[0] >= D ? 1u : 0u) + (k[1] && f[1] >= D ? 1u : 0u) + (k[2] && f[2] >= D ? 1u : 0u) + (k[3] && f[3] >= D ? 1u : 0u);
-            const uint32_t cnt[REINA_COURSE_S_DIED_OUTSIDE + 1] = {
-                (uint32_t)__popcll(__ballot(inf)), (uint32_t)__popcll(__ballot(k[0])), (uint32_t)__popcll(__ballot(k[1])),
-                (uint32_t)__popcll(__ballot(k[2])), (uint32_t)__popcll(__ballot(k[3])),
-                (uint32_t)__popcll(__ballot(inf && (w[j] & RH_DETECTED) && f[0] == TXL_NONE)),
-                (uint32_t)wave_sum((unsigned long long)oor), (uint32_t)__popcll(__ballot(dead && (w[j] & RH_POD_OUTSIDE)))};
-            if (lane == 0) {
+            if (inf) g = s_ages.group_of(idx[j]);
+            // the scalars (out_of_range: one predicate a date)
+            wave_tally(&s_sc[REINA_COURSE_S_INFECTED], inf);
 #pragma unroll
-                for (int c = 0; c <= REINA_COURSE_S_DIED_OUTSIDE; c++)
-                    if (cnt[c]) atomicAdd(&s_sc[c], cnt[c]);
+            for (int c = 0; c < 4; c++) {
+                wave_tally(&s_sc[REINA_COURSE_S_WITH_DETECTION + c], k[c]);
+                wave_tally(&s_sc[REINA_COURSE_S_OUT_OF_RANGE], k[c] && f[c] >= D);
             }
+            wave_tally(&s_sc[REINA_COURSE_S_DETECTED_UNDATED], inf && (w[j] & RH_DETECTED) && f[0] == TXL_NONE);
+            wave_tally(&s_sc[REINA_COURSE_S_DIED_OUTSIDE], dead && (w[j] & RH_POD_OUTSIDE));
             // the delays (LDS)
             const bool ward = k[3] && k[1] && f[2] == TXL_NONE, unit = k[3] && k[2];
             crs_delay(s_h, s_sum, 0u, g, k[0] && ok, det - o + REINA_COURSE_DETECTION_SHIFT);
@@ -246,7 +228,7 @@ static void free_course(reina_course *c) {
 // the log's launch of the day with a course attached (txlog_launch_day)
 static int course_launch_day(reina_txlog *l, uint32_t grid, uint32_t day, uint32_t by_hot, hipStream_t s) {
     const uint32_t N = l->e0->cfg.n_agents, K = (uint32_t)l->members.size();
-    launch_members(k_course_day, l->g, grid, K, CRS_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, l->course->d_rec, l->stride, N, day, by_hot);
+    launch_members(k_course_day, l->g, grid, K, REPORT_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, l->course->d_rec, l->stride, N, day, by_hot);
     return REINA_OK;
 }
 
@@ -271,8 +253,8 @@ int reina_course_create(reina_txlog_t *l, void *stream, reina_course_t **out) {
     hipStream_t s = (hipStream_t)stream;
     const uint32_t N = l->e0->cfg.n_agents, K = (uint32_t)l->members.size();
     HIP_CHECK(hipMalloc(&c->d_rec, sizeof(crs_rec) * l->stride * K));
-    const uint32_t grid = txlog_grid(l, ((N + 3u) / 4u + CRS_THREADS - 1u) / CRS_THREADS);
-    launch_members(k_course_begin, l->g, grid, K, CRS_THREADS, s, l->d_refs, l->e0->h_ref, c->d_rec, l->stride, N);
+    const uint32_t grid = txlog_grid(l, ((N + 3u) / 4u + REPORT_THREADS - 1u) / REPORT_THREADS);
+    launch_members(k_course_begin, l->g, grid, K, REPORT_THREADS, s, l->d_refs, l->e0->h_ref, c->d_rec, l->stride, N);
     c->log = l;
     l->course = c.get();
     *out = c.release();
@@ -289,14 +271,11 @@ int reina_course_report(reina_course_t *course, const uint8_t *age_group, uint32
     if (int rc = course_live(course)) return rc;
     reina_txlog *l = course->log;
     hipStream_t s = (hipStream_t)stream;
-    TxlArgs a;
-    uint32_t grid;
-    if (int rc = day_report(l, "course report", REINA_COURSE_MAX_GROUPS, [](uint32_t d) -> size_t { return REINA_COURSE_REPORT_WORDS(d); }, age_group, n_groups, n_days,
-                            dev_report, s, &a, &grid))
-        return rc;
-    const uint32_t K = (uint32_t)l->members.size();
-    launch_members(k_course_report, l->g, grid, K, CRS_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, course->d_rec, l->stride, dev_report, a);
-    return REINA_OK;
+    return day_report(l, "course report", REINA_COURSE_MAX_GROUPS, REINA_COURSE_REPORT_WORDS(n_days), age_group, n_groups, n_days, dev_report, s,
+                      [&](const TxlArgs &a, uint32_t grid, uint32_t K) -> int {
+                          launch_members(k_course_report, l->g, grid, K, REPORT_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, course->d_rec, l->stride, dev_report, a);
+                          return REINA_OK;
+                      });
 }
 
 int reina_course_read(reina_course_t *course, uint32_t member, uint64_t *out_host, void *stream) {

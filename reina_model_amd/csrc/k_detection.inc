@@ -21,7 +21,7 @@ static_assert(REINA_DETECT_PHASE == 512u && REINA_DETECT_AT_LARGE == 576u && REI
               "report layout");
 static_assert(REINA_DETECT_MAX_GROUPS == REINA_TXLOG_MAX_GROUPS, "the groups are the log report's");
 static_assert(REINA_DETECT_SEVERITIES == 8 && REINA_DETECT_CLASSES == 4, "RH_SEV has three bits; four detection classes");
-static_assert(REINA_DETECT_FIXED_WORDS * 4u + DET_SUMS * 8u + (REINA_MAX_AGES + 1) * 4u + REINA_MAX_AGES <= 16u * 1024u, "LDS budget of k_detect_report");
+static_assert(REINA_DETECT_FIXED_WORDS * 4u + DET_SUMS * 8u + sizeof(ReportAges) <= 16u * 1024u, "LDS budget of k_detect_report");
 static_assert((size_t)REINA_MAX_DAYS * REINA_DETECT_MAX_GROUPS * REINA_DETECT_COHORT_FIELDS < (1u << 30), "table cells are int keys");
 
 // the detection class of a record's detection field and the agent's hot word
@@ -37,22 +37,19 @@ __global__ __launch_bounds__(REPORT_THREADS) void k_detect_report(const MemberRe
                                                                  size_t stride, uint64_t *report, const TxlArgs a) {
     __shared__ uint32_t s_t[REINA_DETECT_FIXED_WORDS];   // the fixed tables and the scalars, at the block's own offsets (the sums' cells stay 0)
     __shared__ unsigned long long s_sum[DET_SUMS];       // at_large_sum, offspring_sum
-    __shared__ int32_t s_as[REINA_MAX_AGES + 1];
-    __shared__ uint8_t s_grp[REINA_MAX_AGES];
+    __shared__ ReportAges s_ages;
     MEMBER_OF_LAUNCH;
     const GAS uint32_t *hot = (const GAS uint32_t *)mref_.B.hot;
     const GAS reina_cold_t *cold = (const GAS reina_cold_t *)mref_.B.cold;
-    const GAS uint32_t *L = (const GAS uint32_t *)log + (GROUP ? (size_t)blockIdx.y * stride : 0u);
-    const GAS crs_rec *C = (const GAS crs_rec *)rec + (GROUP ? (size_t)blockIdx.y * stride : 0u);
-    GAS unsigned long long *R = (GAS unsigned long long *)report + (GROUP ? (size_t)blockIdx.y * REINA_DETECT_REPORT_WORDS(a.n_days) : 0u);
+    const GAS uint32_t *L = member_block<GROUP>(log, stride);
+    const GAS crs_rec *C = member_block<GROUP>(rec, stride);
+    GAS unsigned long long *R = member_block<GROUP>((unsigned long long *)report, REINA_DETECT_REPORT_WORDS(a.n_days));
     const uint32_t tid = threadIdx.x;
     for (uint32_t k = tid; k < REINA_DETECT_FIXED_WORDS; k += REPORT_THREADS) s_t[k] = 0u;
     if (tid < DET_SUMS) s_sum[tid] = 0ull;
-    if (tid <= REINA_MAX_AGES) s_as[tid] = a.p.age_start[tid];
-    if (tid < REINA_MAX_AGES) s_grp[tid] = a.p.group[tid];
+    s_ages.load(a.p);
     __syncthreads();
     const uint32_t N = a.p.n_agents, D = a.n_days, tiles = (N + REPORT_TILE - 1u) / REPORT_TILE;
-    const int top = (int)a.p.nr_ages - 1;
     uint32_t *s_sc = s_t + REINA_DETECT_SCALARS;
     GAS unsigned long long *coh_t = R + REINA_DETECT_COHORT(D), *det_t = R + REINA_DETECT_DETECTIONS(D), *lnk_t = R + REINA_DETECT_LINKS_BY_DAY(D);
     for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
@@ -89,13 +86,13 @@ __global__ __launch_bounds__(REPORT_THREADS) void k_detect_report(const MemberRe
                 cls = ti < ds ? 1 : (ti == ds ? 2 : 3);
             const bool ahead = linked && (cls == 1 || cls == 2);
             int g = 0, gs = 0;
-            if (inf) g = (int)s_grp[age_of(s_as, l.idx[j], 0, top)];
-            if (linked) gs = (int)s_grp[age_of(s_as, (uint32_t)l.src[j], 0, top)];
-            // the scalars beyond load_links' four
+            if (inf) g = s_ages.group_of(l.idx[j]);
+            if (linked) gs = s_ages.group_of((uint32_t)l.src[j]);
+            // the scalars beyond load_links' four (the class scalars differ by lane; out_of_range: one predicate a date)
             wave_count(s_sc, inf ? (int)REINA_DETECT_S_NEVER + dc : -1);
-            wave_count(s_sc, linked && cls == 3 ? (int)REINA_DETECT_S_BREACH : -1);
-            wave_count(s_sc, tk && ti >= D ? (int)REINA_DETECT_S_OUT_OF_RANGE : -1);
-            wave_count(s_sc, dated && det >= D ? (int)REINA_DETECT_S_OUT_OF_RANGE : -1);
+            wave_tally(&s_sc[REINA_DETECT_S_BREACH], linked && cls == 3);
+            wave_tally(&s_sc[REINA_DETECT_S_OUT_OF_RANGE], tk && ti >= D);
+            wave_tally(&s_sc[REINA_DETECT_S_OUT_OF_RANGE], dated && det >= D);
             // the fixed tables (LDS)
             wave_count(s_t, inf ? (int)REINA_DETECT_ASCERTAIN + (g * REINA_DETECT_SEVERITIES + (int)sev) * REINA_DETECT_CLASSES + dc : -1);
             wave_count(s_t, dated ? (int)REINA_DETECT_PHASE + g * REINA_DETECT_PHASES + ph : -1);
@@ -143,14 +140,11 @@ int reina_detect_report(reina_course_t *course, const uint8_t *age_group, uint32
     if (int rc = course_live(course)) return rc;
     reina_txlog *l = course->log;
     hipStream_t s = (hipStream_t)stream;
-    TxlArgs a;
-    uint32_t grid;
-    if (int rc = day_report(l, "detection report", REINA_DETECT_MAX_GROUPS, [](uint32_t d) -> size_t { return REINA_DETECT_REPORT_WORDS(d); }, age_group, n_groups, n_days,
-                            dev_report, s, &a, &grid))
-        return rc;
-    const uint32_t K = (uint32_t)l->members.size();
-    launch_members(k_detect_report, l->g, grid, K, REPORT_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, course->d_rec, l->stride, dev_report, a);
-    return REINA_OK;
+    return day_report(l, "detection report", REINA_DETECT_MAX_GROUPS, REINA_DETECT_REPORT_WORDS(n_days), age_group, n_groups, n_days, dev_report, s,
+                      [&](const TxlArgs &a, uint32_t grid, uint32_t K) -> int {
+                          launch_members(k_detect_report, l->g, grid, K, REPORT_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, course->d_rec, l->stride, dev_report, a);
+                          return REINA_OK;
+                      });
 }
 
 }  // extern "C"

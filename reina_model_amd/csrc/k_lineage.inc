@@ -4,7 +4,7 @@
 //
 // A report reads the hot words, the cold records and the log and writes nothing but the caller's scratch and report block.  The
 // member is a TxMember (k_transmission.inc): scratch = pairs [2][N] | size [N] | alive [N], the last at size + N; the member's
-// log words sit at blockIdx.y * stride of the log's, as in k_txlog_report.  Five kinds of launch:
+// log words are its block of the log's (member_block), as in k_txlog_report.  Five kinds of launch:
 //   k_lineage_links   streams hot + log, gathers the cold record of infected agents and hot + log of their infectors; the tables
 //                     by period (too large for LDS at 256 periods) go to global atomics aggregated in the wave, the link
 //                     scalars to LDS; writes every agent's (parent, distance) pair exactly as k_tx_links does and zeroes its
@@ -40,26 +40,23 @@ __device__ __forceinline__ bool lin_alive(uint32_t w) { return RH_STATE(w) >= RS
 
 // 256 threads, tiles of 512 agents (two per thread), the workgroup's tiles strided over the grid
 template <bool GROUP>
-__global__ __launch_bounds__(TX_THREADS) void k_lineage_links(const TxMember *M_, const TxMember one_, const uint32_t *log, size_t stride,
-                                                              const LinArgs a) {
+__global__ __launch_bounds__(REPORT_THREADS) void k_lineage_links(const TxMember *M_, const TxMember one_, const uint32_t *log, size_t stride,
+                                                                  const LinArgs a) {
     __shared__ uint32_t s_cnt[5];   // infected, roots, linked, bad links, undated
-    __shared__ int32_t s_as[REINA_MAX_AGES + 1];
-    __shared__ uint8_t s_grp[REINA_MAX_AGES];
+    __shared__ ReportAges s_ages;
     const TxMember m = tx_member<GROUP>(M_, one_);
     const GAS uint32_t *hot = (const GAS uint32_t *)m.hot;
     const GAS reina_cold_t *cold = (const GAS reina_cold_t *)m.cold;
-    const GAS uint32_t *L = (const GAS uint32_t *)log + (GROUP ? (size_t)blockIdx.y * stride : 0u);
-    const uint32_t N = a.t.p.n_agents, P = a.P, tiles = (N + TX_TILE - 1u) / TX_TILE;
+    const GAS uint32_t *L = member_block<GROUP>(log, stride);
+    const uint32_t N = a.t.p.n_agents, P = a.P, tiles = (N + REPORT_TILE - 1u) / REPORT_TILE;
     GAS uint64_t *pairs = (GAS uint64_t *)m.pairs;
     GAS uint32_t *size = (GAS uint32_t *)m.size, *alive = size + N;
     GAS unsigned long long *R = (GAS unsigned long long *)m.report;
     GAS unsigned long long *coh = R + REINA_LINEAGE_COHORT(P), *mix_t = R + REINA_LINEAGE_MIXING_T(P), *mix_c = R + REINA_LINEAGE_MIXING_C(P);
     const uint32_t tid = threadIdx.x;
     if (tid < 5) s_cnt[tid] = 0u;
-    if (tid <= REINA_MAX_AGES) s_as[tid] = a.t.p.age_start[tid];
-    if (tid < REINA_MAX_AGES) s_grp[tid] = a.t.p.group[tid];
+    s_ages.load(a.t.p);
     __syncthreads();
-    const int top = (int)a.t.p.nr_ages - 1;
     for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         Links l;
         const bool any = load_links<true>(l, t, N, hot, cold, L, s_cnt, 0, 1, 2, 3);   // (a tile without infected agents still writes its pairs)
@@ -69,10 +66,9 @@ __global__ __launch_bounds__(TX_THREADS) void k_lineage_links(const TxMember *M_
             if (any) {
                 const uint32_t ci = lin_pc(l.lw[j] & 0xFFFFu, a), cs = lin_pc(l.sl[j] & 0xFFFFu, a);
                 int gi = 0, gs = 0;
-                if (l.inf[j]) gi = (int)s_grp[age_of(s_as, i, 0, top)];
-                if (l.linked[j]) gs = (int)s_grp[age_of(s_as, (uint32_t)l.src[j], 0, top)];
-                const uint32_t nu = (uint32_t)__popcll(__ballot(l.inf[j] && ci == P));
-                if ((tid & 63u) == 0u && nu) atomicAdd(&s_cnt[4], nu);
+                if (l.inf[j]) gi = s_ages.group_of(i);
+                if (l.linked[j]) gs = s_ages.group_of((uint32_t)l.src[j]);
+                wave_tally(&s_cnt[4], l.inf[j] && ci == P);
                 const int ck = l.inf[j] ? (int)((ci * REINA_LINEAGE_MAX_GROUPS + (uint32_t)gi) * REINA_LINEAGE_COHORT_FIELDS) : -1;
                 wave_add(coh, ck, 1ull);
                 wave_add(coh + 1, ck, RH_STATE(l.w[j]) >= RS_RECOVERED ? 1ull : 0ull);
@@ -98,14 +94,14 @@ __global__ __launch_bounds__(TX_THREADS) void k_lineage_links(const TxMember *M_
 
 // 256 threads, one agent per thread, strided over the grid
 template <bool GROUP>
-__global__ __launch_bounds__(TX_THREADS) void k_lineage_tally(const TxMember *M_, const TxMember one_, const uint32_t *log, size_t stride,
-                                                              const LinArgs a) {
+__global__ __launch_bounds__(REPORT_THREADS) void k_lineage_tally(const TxMember *M_, const TxMember one_, const uint32_t *log, size_t stride,
+                                                                  const LinArgs a) {
     __shared__ uint32_t s_key[TX_HASH], s_size[TX_HASH], s_alive[TX_HASH];
     __shared__ uint32_t s_unconv, s_alive_agents;
     const TxMember m = tx_member<GROUP>(M_, one_);
-    const GAS uint32_t *L = (const GAS uint32_t *)log + (GROUP ? (size_t)blockIdx.y * stride : 0u);
+    const GAS uint32_t *L = member_block<GROUP>(log, stride);
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    for (uint32_t k = tid; k < TX_HASH; k += TX_THREADS) {
+    for (uint32_t k = tid; k < TX_HASH; k += REPORT_THREADS) {
         s_key[k] = TX_MARK;
         s_size[k] = s_alive[k] = 0u;
     }
@@ -116,9 +112,9 @@ __global__ __launch_bounds__(TX_THREADS) void k_lineage_tally(const TxMember *M_
     uint32_t *size = m.size, *alive = m.size + N;
     GAS unsigned long long *R = (GAS unsigned long long *)m.report;
     GAS unsigned long long *seed = R + REINA_LINEAGE_SEED(P), *lin = R + REINA_LINEAGE_LINEAGE(P);
-    const uint32_t step = gridDim.x * TX_THREADS;
-    const uint32_t end = (N + TX_THREADS - 1u) / TX_THREADS * TX_THREADS;   // (whole waves run the loop)
-    for (uint32_t i = blockIdx.x * TX_THREADS + tid; i < end; i += step) {
+    const uint32_t step = gridDim.x * REPORT_THREADS;
+    const uint32_t end = (N + REPORT_THREADS - 1u) / REPORT_THREADS * REPORT_THREADS;   // (whole waves run the loop)
+    for (uint32_t i = blockIdx.x * REPORT_THREADS + tid; i < end; i += step) {
         uint64_t p = (uint64_t)TX_MARK;
         uint32_t w = 0u, lw = 0u;
         if (i < N) {
@@ -136,11 +132,8 @@ __global__ __launch_bounds__(TX_THREADS) void k_lineage_tally(const TxMember *M_
         const int sk = conv ? (int)(sc * REINA_LINEAGE_SEED_FIELDS) : -1;
         wave_add(seed + 2, sk, 1ull);
         wave_add(seed + 3, sk, al ? 1ull : 0ull);
-        const uint32_t nu = (uint32_t)__popcll(__ballot(infected && !conv)), na = (uint32_t)__popcll(__ballot(al));
-        if (lane == 0) {
-            if (nu) atomicAdd(&s_unconv, nu);
-            if (na) atomicAdd(&s_alive_agents, na);
-        }
+        wave_tally(&s_unconv, infected && !conv);
+        wave_tally(&s_alive_agents, al);
         // tree sizes and alive counts: the lanes that share the first converged lane's root add once
         const uint32_t key = conv ? parent : TX_MARK;
         const uint64_t act = __ballot(conv);
@@ -160,7 +153,7 @@ __global__ __launch_bounds__(TX_THREADS) void k_lineage_tally(const TxMember *M_
         }
     }
     __syncthreads();
-    for (uint32_t k = tid; k < TX_HASH; k += TX_THREADS)
+    for (uint32_t k = tid; k < TX_HASH; k += REPORT_THREADS)
         if (s_key[k] != TX_MARK) {
             if (s_size[k]) atomicAdd(&size[s_key[k]], s_size[k]);
             if (s_alive[k]) atomicAdd(&alive[s_key[k]], s_alive[k]);
@@ -173,27 +166,27 @@ __global__ __launch_bounds__(TX_THREADS) void k_lineage_tally(const TxMember *M_
 
 // 256 threads, one agent per thread, strided over the grid; a non-zero size is the head of a tree
 template <bool GROUP>
-__global__ __launch_bounds__(TX_THREADS) void k_lineage_roots(const TxMember *M_, const TxMember one_, const uint32_t *log, size_t stride,
-                                                              const LinArgs a) {
+__global__ __launch_bounds__(REPORT_THREADS) void k_lineage_roots(const TxMember *M_, const TxMember one_, const uint32_t *log, size_t stride,
+                                                                  const LinArgs a) {
     __shared__ uint32_t s_ts[LIN_Q_MAX * REINA_LINEAGE_SIZE_BINS];
     __shared__ uint32_t s_seed[LIN_Q_MAX * 2u];   // trees, alive trees
     __shared__ uint32_t s_trees, s_alive_trees;
     __shared__ unsigned long long s_big;
     const TxMember m = tx_member<GROUP>(M_, one_);
-    const GAS uint32_t *L = (const GAS uint32_t *)log + (GROUP ? (size_t)blockIdx.y * stride : 0u);
+    const GAS uint32_t *L = member_block<GROUP>(log, stride);
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t N = a.t.p.n_agents, P = a.P, Q = P + 1u;
-    for (uint32_t k = tid; k < Q * REINA_LINEAGE_SIZE_BINS; k += TX_THREADS) s_ts[k] = 0u;
-    for (uint32_t k = tid; k < Q * 2u; k += TX_THREADS) s_seed[k] = 0u;
+    for (uint32_t k = tid; k < Q * REINA_LINEAGE_SIZE_BINS; k += REPORT_THREADS) s_ts[k] = 0u;
+    for (uint32_t k = tid; k < Q * 2u; k += REPORT_THREADS) s_seed[k] = 0u;
     if (tid == 0) {
         s_trees = s_alive_trees = 0u;
         s_big = 0ull;
     }
     __syncthreads();
     const uint32_t *size = m.size, *alive = m.size + N;
-    const uint32_t step = gridDim.x * TX_THREADS;
-    const uint32_t end = (N + TX_THREADS - 1u) / TX_THREADS * TX_THREADS;
-    for (uint32_t i = blockIdx.x * TX_THREADS + tid; i < end; i += step) {
+    const uint32_t step = gridDim.x * REPORT_THREADS;
+    const uint32_t end = (N + REPORT_THREADS - 1u) / REPORT_THREADS * REPORT_THREADS;
+    for (uint32_t i = blockIdx.x * REPORT_THREADS + tid; i < end; i += step) {
         const uint32_t s = i < N ? size[i] : 0u;
         unsigned long long key = 0ull;
         bool al = false;
@@ -205,18 +198,15 @@ __global__ __launch_bounds__(TX_THREADS) void k_lineage_roots(const TxMember *M_
             if (al) atomicAdd(&s_seed[sc * 2u + 1u], 1u);
             key = ((unsigned long long)s << 32) | (unsigned long long)(~i);
         }
-        const uint32_t nt = (uint32_t)__popcll(__ballot(s != 0u)), na = (uint32_t)__popcll(__ballot(al));
+        wave_tally(&s_trees, s != 0u);
+        wave_tally(&s_alive_trees, al);
         key = wave_max(key);
-        if (lane == 0) {
-            if (nt) atomicAdd(&s_trees, nt);
-            if (na) atomicAdd(&s_alive_trees, na);
-            if (key) atomicMax(&s_big, key);
-        }
+        if (lane == 0 && key) atomicMax(&s_big, key);
     }
     __syncthreads();
     GAS unsigned long long *R = (GAS unsigned long long *)m.report;
     flush_lds(s_ts, Q * REINA_LINEAGE_SIZE_BINS, R + REINA_LINEAGE_TREE_SIZES(P));
-    for (uint32_t k = tid; k < Q * 2u; k += TX_THREADS)
+    for (uint32_t k = tid; k < Q * 2u; k += REPORT_THREADS)
         if (s_seed[k]) atomicAdd(&R[REINA_LINEAGE_SEED(P) + (k >> 1) * REINA_LINEAGE_SEED_FIELDS + (k & 1u)], (unsigned long long)s_seed[k]);
     if (tid == 0) {
         if (s_trees) atomicAdd(&R[REINA_LINEAGE_SCALARS + REINA_LINEAGE_S_TREES], (unsigned long long)s_trees);
@@ -255,10 +245,10 @@ static int lineage_launch(const reina_txlog *l, const TxMember *d_m, const TxMem
     const uint32_t K = (uint32_t)l->members.size(), n_cus = l->e0->n_cus;
     HIP_CHECK(hipMemsetAsync(report, 0, (size_t)K * REINA_LINEAGE_REPORT_WORDS(a.P) * 8u, s));
     const ForestPasses f = forest_passes(a.t.p.n_agents, K, n_cus, a.t.host_rounds);
-    launch_members(k_lineage_links, d_m, f.g_links, K, TX_THREADS, s, d_m, one, l->d_log, l->stride, a);
-    for (uint32_t r = 0; r < f.rounds; r++) launch_members(k_tx_jump, d_m, f.g_jump, K, TX_THREADS, s, d_m, one, a.t, r);
-    launch_members(k_lineage_tally, d_m, f.g_tally, K, TX_THREADS, s, d_m, one, l->d_log, l->stride, a);
-    launch_members(k_lineage_roots, d_m, f.g_tally, K, TX_THREADS, s, d_m, one, l->d_log, l->stride, a);
+    launch_members(k_lineage_links, d_m, f.g_links, K, REPORT_THREADS, s, d_m, one, l->d_log, l->stride, a);
+    for (uint32_t r = 0; r < f.rounds; r++) launch_members(k_tx_jump, d_m, f.g_jump, K, REPORT_THREADS, s, d_m, one, a.t, r);
+    launch_members(k_lineage_tally, d_m, f.g_tally, K, REPORT_THREADS, s, d_m, one, l->d_log, l->stride, a);
+    launch_members(k_lineage_roots, d_m, f.g_tally, K, REPORT_THREADS, s, d_m, one, l->d_log, l->stride, a);
     launch_members(k_lineage_finish, d_m, 1u, K, 64, s, d_m, one, a);
     return REINA_OK;
 }

@@ -20,8 +20,6 @@
 // GROUP: the member is element blockIdx.y of a table read through the constant address space; otherwise `one_`, by value.
 #include "../../include/reina_transmission.h"
 
-#define TX_THREADS REPORT_THREADS
-#define TX_TILE REPORT_TILE
 #define TX_MARK 0xFFFFFFFFu        // parent of an agent that is not infected (and an empty hash slot)
 #define TX_ROOTED 0x80000000u      // distance word: the parent is a root
 #define TX_DIST_MAX 0x7FFFFFFFu    // distances saturate (a cycle of bad data doubles them every round)
@@ -63,28 +61,25 @@ __device__ __forceinline__ uint32_t tx_member_rounds(const TxMember &m, const Tx
 // ---------------------------------------------------------------------------------------------
 // k_tx_links: 256 threads, tiles of 512 agents (two per thread), the workgroup's tiles strided over the grid
 template <bool GROUP>
-__global__ __launch_bounds__(TX_THREADS) void k_tx_links(const TxMember *M_, const TxMember one_, const TxArgs a) {
+__global__ __launch_bounds__(REPORT_THREADS) void k_tx_links(const TxMember *M_, const TxMember one_, const TxArgs a) {
     __shared__ uint32_t s_off[TX_CELLS];
     __shared__ uint32_t s_mat[TX_MATRIX_CELLS];
     __shared__ unsigned long long s_sum[TX_SUMS], s_sq[TX_SUMS];
     __shared__ uint32_t s_cnt[4];   // infected, roots, linked, bad links
-    __shared__ int32_t s_as[REINA_MAX_AGES + 1];
-    __shared__ uint8_t s_grp[REINA_MAX_AGES];
+    __shared__ ReportAges s_ages;
     const TxMember m = tx_member<GROUP>(M_, one_);
     const GAS uint32_t *hot = (const GAS uint32_t *)m.hot;
     const GAS reina_cold_t *cold = (const GAS reina_cold_t *)m.cold;
     GAS uint64_t *pairs = (GAS uint64_t *)m.pairs;
     GAS uint32_t *size = (GAS uint32_t *)m.size;
     const uint32_t tid = threadIdx.x;
-    for (uint32_t k = tid; k < TX_CELLS; k += TX_THREADS) s_off[k] = 0u;
-    for (uint32_t k = tid; k < TX_MATRIX_CELLS; k += TX_THREADS) s_mat[k] = 0u;
+    for (uint32_t k = tid; k < TX_CELLS; k += REPORT_THREADS) s_off[k] = 0u;
+    for (uint32_t k = tid; k < TX_MATRIX_CELLS; k += REPORT_THREADS) s_mat[k] = 0u;
     if (tid < TX_SUMS) s_sum[tid] = s_sq[tid] = 0ull;
     if (tid < 4) s_cnt[tid] = 0u;
-    if (tid <= REINA_MAX_AGES) s_as[tid] = a.p.age_start[tid];
-    if (tid < REINA_MAX_AGES) s_grp[tid] = a.p.group[tid];
+    s_ages.load(a.p);
     __syncthreads();
-    const uint32_t N = a.p.n_agents, tiles = (N + TX_TILE - 1u) / TX_TILE;
-    const int top = (int)a.p.nr_ages - 1;
+    const uint32_t N = a.p.n_agents, tiles = (N + REPORT_TILE - 1u) / REPORT_TILE;
     for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         Links l;
         load_links<false>(l, t, N, hot, cold, nullptr, s_cnt, 0, 1, 2, 3);   // (a tile without infected agents still writes its pairs)
@@ -102,7 +97,7 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_links(const TxMember *M_, con
                 atomicAdd(&s_sq[v * REINA_TX_OUTCOMES + o], (unsigned long long)n * n);
             }
             if (l.linked[j]) {
-                const uint32_t gs = s_grp[age_of(s_as, i, 0, top)], gi = s_grp[age_of(s_as, (uint32_t)l.src[j], 0, top)];
+                const uint32_t gs = (uint32_t)s_ages.group_of(i), gi = (uint32_t)s_ages.group_of((uint32_t)l.src[j]);
                 atomicAdd(&s_mat[(v * REINA_TX_MAX_GROUPS + gi) * REINA_TX_MAX_GROUPS + gs], 1u);
             }
             if (i < N) {
@@ -127,13 +122,13 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_links(const TxMember *M_, con
 
 // k_tx_jump: round r of pointer jumping, one thread per agent (grid-strided)
 template <bool GROUP>
-__global__ __launch_bounds__(TX_THREADS) void k_tx_jump(const TxMember *M_, const TxMember one_, const TxArgs a, uint32_t r) {
+__global__ __launch_bounds__(REPORT_THREADS) void k_tx_jump(const TxMember *M_, const TxMember one_, const TxArgs a, uint32_t r) {
     const TxMember m = tx_member<GROUP>(M_, one_);
     if (r >= tx_member_rounds(m, a)) return;
     const uint32_t N = a.p.n_agents;
     const uint64_t *src = m.pairs + (size_t)(r & 1u) * N;
     uint64_t *dst = m.pairs + (size_t)((r + 1u) & 1u) * N;
-    for (uint32_t i = blockIdx.x * TX_THREADS + threadIdx.x; i < N; i += gridDim.x * TX_THREADS) {
+    for (uint32_t i = blockIdx.x * REPORT_THREADS + threadIdx.x; i < N; i += gridDim.x * REPORT_THREADS) {
         uint64_t p = src[i];
         const uint32_t parent = (uint32_t)p, d = (uint32_t)(p >> 32);
         if (parent < N && !(d & TX_ROOTED)) {
@@ -163,15 +158,15 @@ __device__ __forceinline__ void tx_hash_add(uint32_t *keys, uint32_t *cnt, uint3
 
 // k_tx_tally: 256 threads, one agent per thread, strided over the grid
 template <bool GROUP>
-__global__ __launch_bounds__(TX_THREADS) void k_tx_tally(const TxMember *M_, const TxMember one_, const TxArgs a) {
+__global__ __launch_bounds__(REPORT_THREADS) void k_tx_tally(const TxMember *M_, const TxMember one_, const TxArgs a) {
     static_assert(TX_HASH == 1u << 12, "tx_hash_add takes 12 bits");
     __shared__ uint32_t s_gen[REINA_TX_VARIANTS * REINA_TX_GENERATIONS];
     __shared__ uint32_t s_key[TX_HASH], s_cnt[TX_HASH];
     __shared__ uint32_t s_unconv, s_maxgen;
     const TxMember m = tx_member<GROUP>(M_, one_);
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    for (uint32_t k = tid; k < REINA_TX_VARIANTS * REINA_TX_GENERATIONS; k += TX_THREADS) s_gen[k] = 0u;
-    for (uint32_t k = tid; k < TX_HASH; k += TX_THREADS) {
+    for (uint32_t k = tid; k < REINA_TX_VARIANTS * REINA_TX_GENERATIONS; k += REPORT_THREADS) s_gen[k] = 0u;
+    for (uint32_t k = tid; k < TX_HASH; k += REPORT_THREADS) {
         s_key[k] = TX_MARK;
         s_cnt[k] = 0u;
     }
@@ -179,9 +174,9 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_tally(const TxMember *M_, con
     __syncthreads();
     const uint32_t N = a.p.n_agents;
     const uint64_t *pairs = m.pairs + (size_t)(tx_member_rounds(m, a) & 1u) * N;
-    const uint32_t stride = gridDim.x * TX_THREADS;
-    const uint32_t end = (N + TX_THREADS - 1u) / TX_THREADS * TX_THREADS;   // (whole waves run the loop)
-    for (uint32_t i = blockIdx.x * TX_THREADS + tid; i < end; i += stride) {
+    const uint32_t stride = gridDim.x * REPORT_THREADS;
+    const uint32_t end = (N + REPORT_THREADS - 1u) / REPORT_THREADS * REPORT_THREADS;   // (whole waves run the loop)
+    for (uint32_t i = blockIdx.x * REPORT_THREADS + tid; i < end; i += stride) {
         uint64_t p = (uint64_t)TX_MARK;
         uint32_t w = 0u;
         if (i < N) {
@@ -193,12 +188,9 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_tally(const TxMember *M_, con
         const bool conv = infected && (d & TX_ROOTED) && parent < N;   // (every pair of an infected agent points below N)
         const uint32_t gen = d & TX_DIST_MAX;
         wave_count(s_gen, conv ? (int)(RH_VARIANT(w) * REINA_TX_GENERATIONS + (gen < 255u ? gen : 255u)) : -1);
-        const uint32_t nu = (uint32_t)__popcll(__ballot(infected && !conv));
+        wave_tally(&s_unconv, infected && !conv);
         const uint32_t g = wave_max(conv ? gen : 0u);
-        if (lane == 0) {
-            if (nu) atomicAdd(&s_unconv, nu);
-            if (g) atomicMax(&s_maxgen, g);
-        }
+        if (lane == 0 && g) atomicMax(&s_maxgen, g);
         // tree sizes: the lanes that share the first converged lane's root add once
         const uint32_t key = conv ? parent : TX_MARK;
         const uint64_t act = __ballot(conv);
@@ -215,7 +207,7 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_tally(const TxMember *M_, con
     }
     __syncthreads();
     GAS unsigned long long *R = (GAS unsigned long long *)m.report;
-    for (uint32_t k = tid; k < TX_HASH; k += TX_THREADS)
+    for (uint32_t k = tid; k < TX_HASH; k += REPORT_THREADS)
         if (s_key[k] != TX_MARK) atomicAdd(&m.size[s_key[k]], s_cnt[k]);
     flush_lds(s_gen, REINA_TX_VARIANTS * REINA_TX_GENERATIONS, R + REINA_TX_GENERATION);
     if (tid == 0) {
@@ -226,7 +218,7 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_tally(const TxMember *M_, con
 
 // k_tx_clusters: 256 threads, one agent per thread, strided over the grid; a non-zero size is a root's tree
 template <bool GROUP>
-__global__ __launch_bounds__(TX_THREADS) void k_tx_clusters(const TxMember *M_, const TxMember one_, const TxArgs a) {
+__global__ __launch_bounds__(REPORT_THREADS) void k_tx_clusters(const TxMember *M_, const TxMember one_, const TxArgs a) {
     __shared__ uint32_t s_cl[REINA_TX_CLUSTER_BINS];
     __shared__ unsigned long long s_ca[REINA_TX_CLUSTER_BINS];
     __shared__ unsigned long long s_key;
@@ -239,9 +231,9 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_clusters(const TxMember *M_, 
     if (tid == 0) s_key = 0ull;
     __syncthreads();
     const uint32_t N = a.p.n_agents;
-    const uint32_t stride = gridDim.x * TX_THREADS;
-    const uint32_t end = (N + TX_THREADS - 1u) / TX_THREADS * TX_THREADS;
-    for (uint32_t i = blockIdx.x * TX_THREADS + tid; i < end; i += stride) {
+    const uint32_t stride = gridDim.x * REPORT_THREADS;
+    const uint32_t end = (N + REPORT_THREADS - 1u) / REPORT_THREADS * REPORT_THREADS;
+    for (uint32_t i = blockIdx.x * REPORT_THREADS + tid; i < end; i += stride) {
         const uint32_t s = i < N ? m.size[i] : 0u;
         unsigned long long key = 0ull;
         if (s) {
@@ -287,10 +279,10 @@ static int tx_args(const reina_engine_t *e, const uint8_t *age_group, uint32_t n
 static int tx_launch(const TxMember *d_m, const TxMember &one, const TxArgs &a, uint32_t K, uint32_t n_cus, uint64_t *report, hipStream_t s) {
     HIP_CHECK(hipMemsetAsync(report, 0, (size_t)K * REINA_TX_REPORT_WORDS * 8u, s));
     const ForestPasses f = forest_passes(a.p.n_agents, K, n_cus, a.host_rounds);
-    launch_members(k_tx_links, d_m, f.g_links, K, TX_THREADS, s, d_m, one, a);
-    for (uint32_t r = 0; r < f.rounds; r++) launch_members(k_tx_jump, d_m, f.g_jump, K, TX_THREADS, s, d_m, one, a, r);
-    launch_members(k_tx_tally, d_m, f.g_tally, K, TX_THREADS, s, d_m, one, a);
-    launch_members(k_tx_clusters, d_m, f.g_tally, K, TX_THREADS, s, d_m, one, a);
+    launch_members(k_tx_links, d_m, f.g_links, K, REPORT_THREADS, s, d_m, one, a);
+    for (uint32_t r = 0; r < f.rounds; r++) launch_members(k_tx_jump, d_m, f.g_jump, K, REPORT_THREADS, s, d_m, one, a, r);
+    launch_members(k_tx_tally, d_m, f.g_tally, K, REPORT_THREADS, s, d_m, one, a);
+    launch_members(k_tx_clusters, d_m, f.g_tally, K, REPORT_THREADS, s, d_m, one, a);
     launch_members(k_tx_finish, d_m, 1u, K, 64, s, d_m, one, a);
     return REINA_OK;
 }

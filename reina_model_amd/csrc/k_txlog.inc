@@ -3,10 +3,9 @@
 //
 // Three kernels, each bound by memory traffic:
 //   k_txlog_begin   streams the hot words (16 bytes a lane) and writes every log word.
-//   k_txlog_day     ONE launch a day, queued behind the day's last launch.  It streams the ACTIVE bit plane (N / 8 bytes) in the
-//                   512-agent tiles of 16 words that k_day's sparse stream uses, one tile a wave: lane l looks at agent
-//                   64 j + l of the tile in round j, so the hot words of a dense tile are fetched coalesced.  Two forms of the
-//                   update, chosen per launch:
+//   k_txlog_day     ONE launch a day, queued behind the day's last launch.  It streams the ACTIVE bit plane (N / 8 bytes), one
+//                   512-agent tile a wave (k_addons.inc's active_tile has the geometry).  Two forms of the update, chosen per
+//                   launch:
 //                     by_hot = 0  reads the log word of every active agent and applies the definition to it;
 //                     by_hot = 1  decides from the hot word alone -- INCUBATION with the day in bits 24-31: the agent was infected
 //                                 today, a full-word store; ILLNESS with day + 1 there: its onset was today, a 16-bit store of the
@@ -15,16 +14,15 @@
 //                                 records and on any day that does not follow the last one recorded: the agents an initial
 //                                 condition leaves incubating carry day 0 in bits 24-31 and are BEFORE, not "infected on day 0".
 //   k_txlog_report  streams hot + log, gathers the cold record of infected agents and hot + log of their infectors; the interval
-//                   histograms and the scalars are counted in LDS and flushed once per workgroup; the tables indexed by day
-//                   (too large for LDS at 4096 days) go to global atomics aggregated in the wave: the lanes that share the first
-//                   lane's cell add once (agents are sorted by age and an epidemic's days are few: most of a wave's lanes do).
+//                   histograms (wave_count) and the scalars (wave_tally) are counted in LDS and flushed once per workgroup; the
+//                   tables indexed by day (too large for LDS at 4096 days) go to global atomics aggregated in the wave
+//                   (wave_add): the lanes that share the first lane's cell add once (agents are sorted by age and an epidemic's
+//                   days are few: most of a wave's lanes do).
 // GROUP: the member is element blockIdx.y of the group's member table (MEMBER_OF_LAUNCH), its log words and report block the
-// blockIdx.y-th of the log's; otherwise the one engine by value.  One lane owns an agent: no atomics on the log, no fences (a
-// kernel boundary lies on either side of every launch).
+// blockIdx.y-th of the log's (member_block); otherwise the one engine by value.  One lane owns an agent: no atomics on the log,
+// no fences (a kernel boundary lies on either side of every launch).
 #include "../../include/reina_txlog.h"
 
-#define TXL_THREADS REPORT_THREADS
-#define TXL_TILE REPORT_TILE
 #define TXL_NONE ((uint32_t)REINA_TXLOG_NONE)
 #define TXL_BEFORE ((uint32_t)REINA_TXLOG_BEFORE)
 static_assert(REINA_MAX_DAYS < REINA_TXLOG_BEFORE, "day numbers lie below the codes");
@@ -38,12 +36,12 @@ __host__ __device__ __forceinline__ uint32_t txl_begin_word(uint32_t w) {
 
 // the log is padded to whole tiles (its words beyond n_agents: NONE | NONE, never read back); the hot words are not
 template <bool GROUP>
-__global__ __launch_bounds__(TXL_THREADS) void k_txlog_begin(const MemberRef *M_, const MemberRef one_, uint32_t *log, size_t stride, uint32_t N) {
+__global__ __launch_bounds__(REPORT_THREADS) void k_txlog_begin(const MemberRef *M_, const MemberRef one_, uint32_t *log, size_t stride, uint32_t N) {
     MEMBER_OF_LAUNCH;
     const GAS uint32_t *hot = (const GAS uint32_t *)mref_.B.hot;
-    GAS uint32_t *L = (GAS uint32_t *)log + (GROUP ? (size_t)blockIdx.y * stride : 0u);
+    GAS uint32_t *L = member_block<GROUP>(log, stride);
     const uint32_t quads = (N + 3u) / 4u;
-    for (uint32_t q = blockIdx.x * TXL_THREADS + threadIdx.x; q < quads; q += gridDim.x * TXL_THREADS) {
+    for (uint32_t q = blockIdx.x * REPORT_THREADS + threadIdx.x; q < quads; q += gridDim.x * REPORT_THREADS) {
         const uint32_t i = 4u * q;
         v4u_ w;
         if (i + 3u < N) {
@@ -83,28 +81,21 @@ __device__ __forceinline__ void txl_day_update(GAS uint32_t *L, uint32_t i, uint
 
 // four waves a workgroup, one tile a wave and round, the tiles strided over the grid
 template <bool GROUP>
-__global__ __launch_bounds__(TXL_THREADS) void k_txlog_day(const MemberRef *M_, const MemberRef one_, uint32_t *log, size_t stride, uint32_t N, uint32_t day,
-                                                           uint32_t by_hot) {
+__global__ __launch_bounds__(REPORT_THREADS) void k_txlog_day(const MemberRef *M_, const MemberRef one_, uint32_t *log, size_t stride, uint32_t N, uint32_t day,
+                                                              uint32_t by_hot) {
     MEMBER_OF_LAUNCH;
     const GAS uint32_t *hot = (const GAS uint32_t *)mref_.B.hot;
     const GAS uint32_t *plane = (const GAS uint32_t *)mref_.B.active_bits;
-    GAS uint32_t *L = (GAS uint32_t *)log + (GROUP ? (size_t)blockIdx.y * stride : 0u);
+    GAS uint32_t *L = member_block<GROUP>(log, stride);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t tiles = (N + TXL_TILE - 1u) / TXL_TILE;
+    const uint32_t tiles = (N + REPORT_TILE - 1u) / REPORT_TILE;
     const uint32_t d8 = day & 0xFFu, o8 = (day + 1u) & 0xFFu;
-    for (uint32_t t = blockIdx.x * (TXL_THREADS / 64u) + wave; t < tiles; t += gridDim.x * (TXL_THREADS / 64u)) {
-        const uint32_t wd = plane[t * 16u + (lane & 15u)];   // (the plane holds whole tiles: REINA_BITS_WORDS)
-        if (!__ballot(wd != 0u)) continue;
+    for (uint32_t t = blockIdx.x * (REPORT_THREADS / 64u) + wave; t < tiles; t += gridDim.x * (REPORT_THREADS / 64u)) {
         uint32_t w[8];
+        if (!active_tile(plane, hot, t, N, lane, w)) continue;
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-            const uint32_t bits = (uint32_t)__shfl((int)wd, 2 * j + (int)(lane >> 5));
-            const uint32_t i = t * TXL_TILE + (uint32_t)j * 64u + lane;
-            w[j] = ((bits >> (lane & 31u)) & 1u) && i < N ? hot[i] : 0u;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint32_t i = t * TXL_TILE + (uint32_t)j * 64u + lane;
+            const uint32_t i = t * REPORT_TILE + (uint32_t)j * 64u + lane;
             if (RH_STATE(w[j]) == RS_SUSCEPTIBLE) continue;
             txl_day_update(L, i, w[j], day, d8, o8, by_hot);
         }
@@ -115,25 +106,22 @@ __device__ __forceinline__ int txl_clip(int x, int hi) { return x < 0 ? 0 : (x >
 
 // 256 threads, tiles of 512 agents (two per thread), the workgroup's tiles strided over the grid
 template <bool GROUP>
-__global__ __launch_bounds__(TXL_THREADS) void k_txlog_report(const MemberRef *M_, const MemberRef one_, const uint32_t *log, size_t stride,
-                                                              uint64_t *report, const TxlArgs a) {
+__global__ __launch_bounds__(REPORT_THREADS) void k_txlog_report(const MemberRef *M_, const MemberRef one_, const uint32_t *log, size_t stride,
+                                                                 uint64_t *report, const TxlArgs a) {
     __shared__ uint32_t s_h[REINA_TXLOG_SCALARS];   // the interval histograms and the link phases, at the block's own offsets
     __shared__ uint32_t s_c[REINA_TXLOG_S_NR];
-    __shared__ int32_t s_as[REINA_MAX_AGES + 1];
-    __shared__ uint8_t s_grp[REINA_MAX_AGES];
+    __shared__ ReportAges s_ages;
     MEMBER_OF_LAUNCH;
     const GAS uint32_t *hot = (const GAS uint32_t *)mref_.B.hot;
     const GAS reina_cold_t *cold = (const GAS reina_cold_t *)mref_.B.cold;
-    const GAS uint32_t *L = (const GAS uint32_t *)log + (GROUP ? (size_t)blockIdx.y * stride : 0u);
-    GAS unsigned long long *R = (GAS unsigned long long *)report + (GROUP ? (size_t)blockIdx.y * REINA_TXLOG_REPORT_WORDS(a.n_days) : 0u);
+    const GAS uint32_t *L = member_block<GROUP>(log, stride);
+    GAS unsigned long long *R = member_block<GROUP>((unsigned long long *)report, REINA_TXLOG_REPORT_WORDS(a.n_days));
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    for (uint32_t k = tid; k < REINA_TXLOG_SCALARS; k += TXL_THREADS) s_h[k] = 0u;
+    for (uint32_t k = tid; k < REINA_TXLOG_SCALARS; k += REPORT_THREADS) s_h[k] = 0u;
     if (tid < REINA_TXLOG_S_NR) s_c[tid] = tid == REINA_TXLOG_S_FIRST_DAY ? 0xFFFFFFFFu : 0u;
-    if (tid <= REINA_MAX_AGES) s_as[tid] = a.p.age_start[tid];
-    if (tid < REINA_MAX_AGES) s_grp[tid] = a.p.group[tid];
+    s_ages.load(a.p);
     __syncthreads();
-    const uint32_t N = a.p.n_agents, D = a.n_days, tiles = (N + TXL_TILE - 1u) / TXL_TILE;
-    const int top = (int)a.p.nr_ages - 1;
+    const uint32_t N = a.p.n_agents, D = a.n_days, tiles = (N + REPORT_TILE - 1u) / REPORT_TILE;
     GAS unsigned long long *inc_t = R + REINA_TXLOG_INCIDENCE(D), *ons_t = R + REINA_TXLOG_ONSETS(D), *coh_t = R + REINA_TXLOG_COHORT(D);
     for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         Links l;
@@ -146,23 +134,19 @@ __global__ __launch_bounds__(TXL_THREADS) void k_txlog_report(const MemberRef *M
             const uint32_t ts = l.sl[j] & 0xFFFFu, os = l.sl[j] >> 16;
             const bool linked = l.linked[j], tsk = linked && ts < TXL_BEFORE, osk = linked && os < TXL_BEFORE;
             const bool both = tk && tsk;
-            // the scalars: one LDS atomic a wave and kind
-            const uint32_t oor = (tk && ti >= D ? 1u : 0u) + (ok && oi >= D ? 1u : 0u);
-            const uint32_t cnt[6] = {(uint32_t)__popcll(__ballot(tk)), (uint32_t)__popcll(__ballot(l.inf[j] && ti == TXL_BEFORE)),
-                                     (uint32_t)__popcll(__ballot(ok)), (uint32_t)__popcll(__ballot(both)),
-                                     (uint32_t)__popcll(__ballot(both && ti <= ts)),
-                                     (uint32_t)__popcll(__ballot(oor >= 1u)) + (uint32_t)__popcll(__ballot(oor == 2u))};
+            // the scalars (out_of_range: one predicate a date)
+            wave_tally(&s_c[REINA_TXLOG_S_DATED], tk);
+            wave_tally(&s_c[REINA_TXLOG_S_BEFORE], l.inf[j] && ti == TXL_BEFORE);
+            wave_tally(&s_c[REINA_TXLOG_S_WITH_ONSET], ok);
+            wave_tally(&s_c[REINA_TXLOG_S_LINKS_DATED], both);
+            wave_tally(&s_c[REINA_TXLOG_S_GENERATION_NONPOSITIVE], both && ti <= ts);
+            wave_tally(&s_c[REINA_TXLOG_S_OUT_OF_RANGE], tk && ti >= D);
+            wave_tally(&s_c[REINA_TXLOG_S_OUT_OF_RANGE], ok && oi >= D);
+            // (the first and the last day are a minimum and a maximum, not tallies; lo keeps all ones in a wave without a dated agent)
             const uint32_t lo = wave_min(tk ? ti : 0xFFFFFFFFu), hi = wave_max(tk ? ti : 0u);
-            if (lane == 0) {
-                const uint32_t at[6] = {REINA_TXLOG_S_DATED, REINA_TXLOG_S_BEFORE, REINA_TXLOG_S_WITH_ONSET, REINA_TXLOG_S_LINKS_DATED,
-                                        REINA_TXLOG_S_GENERATION_NONPOSITIVE, REINA_TXLOG_S_OUT_OF_RANGE};
-#pragma unroll
-                for (int k = 0; k < 6; k++)
-                    if (cnt[k]) atomicAdd(&s_c[at[k]], cnt[k]);
-                if (cnt[0]) {
-                    atomicMin(&s_c[REINA_TXLOG_S_FIRST_DAY], lo);
-                    atomicMax(&s_c[REINA_TXLOG_S_LAST_DAY], hi);
-                }
+            if (lane == 0 && lo != 0xFFFFFFFFu) {
+                atomicMin(&s_c[REINA_TXLOG_S_FIRST_DAY], lo);
+                atomicMax(&s_c[REINA_TXLOG_S_LAST_DAY], hi);
             }
             // the interval histograms (LDS)
             wave_count(s_h, tk && ok ? (int)(REINA_TXLOG_INCUBATION + v * REINA_TXLOG_INCUBATION_BINS) +
@@ -182,7 +166,7 @@ __global__ __launch_bounds__(TXL_THREADS) void k_txlog_report(const MemberRef *M
             // the tables by day (global, aggregated in the wave)
             const bool in = tk && ti < D;
             int g = 0;
-            if (in) g = (int)s_grp[age_of(s_as, i, 0, top)];
+            if (in) g = s_ages.group_of(i);
             wave_add(inc_t, in ? (int)((ti * REINA_TXLOG_VARIANTS + v) * REINA_TXLOG_MAX_GROUPS) + g : -1, 1ull);
             wave_add(ons_t, ok && oi < D ? (int)(oi * REINA_TXLOG_VARIANTS + v) : -1, 1ull);
             const int ck = in ? (int)((ti * REINA_TXLOG_VARIANTS + v) * REINA_TXLOG_COHORT_FIELDS) : -1;
@@ -237,10 +221,10 @@ static int txlog_create(const std::vector<reina_engine_t *> &members, reina_grou
     const char *form = std::getenv("REINA_TXLOG_FORM");
     l->by_hot = !(form && std::strcmp(form, "log") == 0);
     const uint32_t N = l->e0->cfg.n_agents, K = (uint32_t)members.size();
-    l->stride = ((size_t)N + TXL_TILE - 1u) / TXL_TILE * TXL_TILE;
+    l->stride = ((size_t)N + REPORT_TILE - 1u) / REPORT_TILE * REPORT_TILE;
     HIP_CHECK(hipMalloc(&l->d_log, sizeof(uint32_t) * l->stride * K));
-    const uint32_t grid = txlog_grid(l.get(), ((N + 3u) / 4u + TXL_THREADS - 1u) / TXL_THREADS);
-    launch_members(k_txlog_begin, g, grid, K, TXL_THREADS, s, d_refs, l->e0->h_ref, l->d_log, l->stride, N);
+    const uint32_t grid = txlog_grid(l.get(), ((N + 3u) / 4u + REPORT_THREADS - 1u) / REPORT_THREADS);
+    launch_members(k_txlog_begin, g, grid, K, REPORT_THREADS, s, d_refs, l->e0->h_ref, l->d_log, l->stride, N);
     *out = l.release();
     return REINA_OK;
 }
@@ -251,12 +235,12 @@ static int txlog_launch_day(reina_txlog *l, uint32_t day, hipStream_t s) {
     const uint32_t N = l->e0->cfg.n_agents, K = (uint32_t)l->members.size();
     // (the hot-word tests hold for the days that follow a recorded day: the first day, and a day after a gap, read the log)
     const uint32_t by_hot = l->by_hot && l->last_day >= 0 && (int64_t)day == l->last_day + 1 ? 1u : 0u;
-    const uint32_t tiles = (N + TXL_TILE - 1u) / TXL_TILE;
-    const uint32_t grid = txlog_grid(l, (tiles + TXL_THREADS / 64u - 1u) / (TXL_THREADS / 64u));
+    const uint32_t tiles = (N + REPORT_TILE - 1u) / REPORT_TILE;
+    const uint32_t grid = txlog_grid(l, (tiles + REPORT_THREADS / 64u - 1u) / (REPORT_THREADS / 64u));
     if (l->course) {
         if (int rc = course_launch_day(l, grid, day, by_hot, s)) return rc;
     } else {
-        launch_members(k_txlog_day, l->g, grid, K, TXL_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, N, day, by_hot);
+        launch_members(k_txlog_day, l->g, grid, K, REPORT_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, N, day, by_hot);
     }
     l->last_day = day;
     return REINA_OK;
@@ -264,15 +248,13 @@ static int txlog_launch_day(reina_txlog *l, uint32_t day, hipStream_t s) {
 static int txlog_after_day(attachment *a, const reina_day_t &d, hipStream_t s) { return txlog_launch_day(static_cast<reina_txlog *>(a), d.day, s); }
 
 static int txlog_report(reina_txlog *l, const uint8_t *age_group, uint32_t n_groups, uint32_t n_days, uint64_t *dev_report, hipStream_t s) {
-    TxlArgs a;
-    uint32_t grid;
-    if (int rc = day_report(l, "txlog report", REINA_TXLOG_MAX_GROUPS, [](uint32_t d) -> size_t { return REINA_TXLOG_REPORT_WORDS(d); }, age_group, n_groups, n_days,
-                            dev_report, s, &a, &grid))
-        return rc;
-    const uint32_t K = (uint32_t)l->members.size();
-    HIP_CHECK(hipMemset2DAsync(dev_report + REINA_TXLOG_SCALARS + REINA_TXLOG_S_FIRST_DAY, REINA_TXLOG_REPORT_WORDS(n_days) * 8u, 0xFF, 8u, K, s));
-    launch_members(k_txlog_report, l->g, grid, K, TXL_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, dev_report, a);
-    return REINA_OK;
+    return day_report(l, "txlog report", REINA_TXLOG_MAX_GROUPS, REINA_TXLOG_REPORT_WORDS(n_days), age_group, n_groups, n_days, dev_report, s,
+                      [&](const TxlArgs &a, uint32_t grid, uint32_t K) -> int {
+                          // (the first day is a minimum: every member's cell starts at all ones)
+                          HIP_CHECK(hipMemset2DAsync(dev_report + REINA_TXLOG_SCALARS + REINA_TXLOG_S_FIRST_DAY, REINA_TXLOG_REPORT_WORDS(n_days) * 8u, 0xFF, 8u, K, s));
+                          launch_members(k_txlog_report, l->g, grid, K, REPORT_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, dev_report, a);
+                          return REINA_OK;
+                      });
 }
 
 extern "C" {

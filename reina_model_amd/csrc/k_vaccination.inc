@@ -17,7 +17,7 @@ static_assert(REINA_VACC_SEVERITY == 0u && REINA_VACC_OUTCOME == 512u && REINA_V
               "report layout");
 static_assert(REINA_VACC_MAX_GROUPS == REINA_TXLOG_MAX_GROUPS, "the groups are the log report's");
 static_assert(REINA_VACC_SEVERITIES == 8 && REINA_VACC_STATUSES == 4 && REINA_VACC_DATED_STATUSES == 3, "RH_SEV has three bits; status 3 has no date");
-static_assert(REINA_VACC_FIXED_WORDS * 4u + (REINA_MAX_AGES + 1) * 4u + REINA_MAX_AGES <= 20u * 1024u, "LDS budget of k_vacc_report");
+static_assert(REINA_VACC_FIXED_WORDS * 4u + sizeof(ReportAges) <= 20u * 1024u, "LDS budget of k_vacc_report");
 static_assert((size_t)REINA_MAX_DAYS * REINA_VACC_MAX_GROUPS * REINA_VACC_DATED_STATUSES < (1u << 30), "table cells are int keys");
 
 // 256 threads, tiles of 512 agents (two per thread), the workgroup's tiles strided over the grid
@@ -25,30 +25,23 @@ template <bool GROUP>
 __global__ __launch_bounds__(REPORT_THREADS) void k_vacc_report(const MemberRef *M_, const MemberRef one_, const uint32_t *log, size_t stride, uint64_t *report,
                                                                const TxlArgs a) {
     __shared__ uint32_t s_t[REINA_VACC_FIXED_WORDS];   // the fixed tables and the scalars, at the block's own offsets
-    __shared__ int32_t s_as[REINA_MAX_AGES + 1];
-    __shared__ uint8_t s_grp[REINA_MAX_AGES];
+    __shared__ ReportAges s_ages;
     MEMBER_OF_LAUNCH;
     const GAS uint32_t *hot = (const GAS uint32_t *)mref_.B.hot;
     const GAS reina_cold_t *cold = (const GAS reina_cold_t *)mref_.B.cold;
-    const GAS uint32_t *L = (const GAS uint32_t *)log + (GROUP ? (size_t)blockIdx.y * stride : 0u);
-    GAS unsigned long long *R = (GAS unsigned long long *)report + (GROUP ? (size_t)blockIdx.y * REINA_VACC_REPORT_WORDS(a.n_days) : 0u);
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const GAS uint32_t *L = member_block<GROUP>(log, stride);
+    GAS unsigned long long *R = member_block<GROUP>((unsigned long long *)report, REINA_VACC_REPORT_WORDS(a.n_days));
+    const uint32_t tid = threadIdx.x;
     for (uint32_t k = tid; k < REINA_VACC_FIXED_WORDS; k += REPORT_THREADS) s_t[k] = 0u;
-    if (tid <= REINA_MAX_AGES) s_as[tid] = a.p.age_start[tid];
-    if (tid < REINA_MAX_AGES) s_grp[tid] = a.p.group[tid];
+    s_ages.load(a.p);
     __syncthreads();
     const uint32_t N = a.p.n_agents, D = a.n_days, tiles = (N + REPORT_TILE - 1u) / REPORT_TILE;
-    const int top = (int)a.p.nr_ages - 1;
     uint32_t *s_sc = s_t + REINA_VACC_SCALARS;
     GAS unsigned long long *vac_t = R + REINA_VACC_VACCINATIONS(D), *inf_t = R + REINA_VACC_INFECTIONS(D), *coh_t = R + REINA_VACC_COHORT(D);
     for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         uint32_t idx[2], w[2], lw[2];
         int32_t vd[2];
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            idx[j] = t * REPORT_TILE + (uint32_t)j * REPORT_THREADS + tid;
-            w[j] = idx[j] < N ? hot[idx[j]] : 0u;
-        }
+        tile_words(t, N, hot, idx, w);
         if (!__ballot(((w[0] | w[1]) & (7u | RH_VACCINATED)) != 0u)) continue;
 #pragma unroll
         for (int j = 0; j < 2; j++) {
@@ -78,19 +71,17 @@ __global__ __launch_bounds__(REPORT_THREADS) void k_vacc_report(const MemberRef 
                 }
             }
             int g = 0;
-            if (inf || vac) g = (int)s_grp[age_of(s_as, idx[j], 0, top)];
+            if (inf || vac) g = s_ages.group_of(idx[j]);
             const bool dated = status >= 0 && status < REINA_VACC_DATED_STATUSES && tk;
-            // the scalars: one LDS atomic a wave and kind
-            const uint32_t oor = (valid && (uint32_t)vd[j] >= D ? 1u : 0u) + (dated && ti >= D ? 1u : 0u);
-            const uint32_t cnt[REINA_VACC_S_OUT_OF_RANGE + 1] = {
-                (uint32_t)__popcll(__ballot(vac)), (uint32_t)__popcll(__ballot(inf)), (uint32_t)__popcll(__ballot(vac && inf)),
-                (uint32_t)__popcll(__ballot(after)), (uint32_t)__popcll(__ballot(status == REINA_VACC_UNDETERMINED)),
-                (uint32_t)__popcll(__ballot(vac && !valid)), (uint32_t)__popcll(__ballot(oor >= 1u)) + (uint32_t)__popcll(__ballot(oor == 2u))};
-            if (lane == 0) {
-#pragma unroll
-                for (int c = 0; c <= REINA_VACC_S_OUT_OF_RANGE; c++)
-                    if (cnt[c]) atomicAdd(&s_sc[c], cnt[c]);
-            }
+            // the scalars (out_of_range: one predicate a date)
+            wave_tally(&s_sc[REINA_VACC_S_VACCINATED], vac);
+            wave_tally(&s_sc[REINA_VACC_S_INFECTED], inf);
+            wave_tally(&s_sc[REINA_VACC_S_VACCINATED_INFECTED], vac && inf);
+            wave_tally(&s_sc[REINA_VACC_S_AFTER_INFECTION], after);
+            wave_tally(&s_sc[REINA_VACC_S_UNDETERMINED], status == REINA_VACC_UNDETERMINED);
+            wave_tally(&s_sc[REINA_VACC_S_BAD_VACC_DAY], vac && !valid);
+            wave_tally(&s_sc[REINA_VACC_S_OUT_OF_RANGE], valid && (uint32_t)vd[j] >= D);
+            wave_tally(&s_sc[REINA_VACC_S_OUT_OF_RANGE], dated && ti >= D);
             // the fixed tables (LDS)
             const int cell = status * REINA_VACC_MAX_GROUPS + g;
             const bool closed = st >= RS_RECOVERED, dead = st == RS_DEAD, severe = sev >= RV_SEVERE;
@@ -132,14 +123,11 @@ int reina_vacc_version(void) { return REINA_VACC_VERSION; }
 int reina_vacc_report(reina_txlog_t *l, const uint8_t *age_group, uint32_t n_groups, uint32_t n_days, uint64_t *dev_report, void *stream) {
     if (!l) return REINA_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    TxlArgs a;
-    uint32_t grid;
-    if (int rc = day_report(l, "vaccination report", REINA_VACC_MAX_GROUPS, [](uint32_t d) -> size_t { return REINA_VACC_REPORT_WORDS(d); }, age_group, n_groups, n_days,
-                            dev_report, s, &a, &grid))
-        return rc;
-    const uint32_t K = (uint32_t)l->members.size();
-    launch_members(k_vacc_report, l->g, grid, K, REPORT_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, dev_report, a);
-    return REINA_OK;
+    return day_report(l, "vaccination report", REINA_VACC_MAX_GROUPS, REINA_VACC_REPORT_WORDS(n_days), age_group, n_groups, n_days, dev_report, s,
+                      [&](const TxlArgs &a, uint32_t grid, uint32_t K) -> int {
+                          launch_members(k_vacc_report, l->g, grid, K, REPORT_THREADS, s, l->d_refs, l->e0->h_ref, l->d_log, l->stride, dev_report, a);
+                          return REINA_OK;
+                      });
 }
 
 }  // extern "C"
