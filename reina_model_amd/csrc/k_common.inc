@@ -66,8 +66,7 @@ struct Tables {  // bigger tables staged into LDS by k_day
     uint32_t age_shift;
     uint8_t age_block[REINA_AGE_BLOCKS];
 };
-#define REINA_LDS_ROWS 28   // distinct contact rows a workgroup keeps in LDS; rows beyond are read through L2
-#define REINA_LDS_CROWS 20  // distinct count rows a workgroup keeps in LDS; rows beyond are read through L2
+#include "reina_launch.h"   // REINA_LDS_ROWS / _CROWS, the block shapes and thresholds of the day's kernels, VaccGeom, the HI_* flags
 
 // Pointers that reach a kernel through MemberRef (an array in HBM) are generic to the compiler, and
 // generic means flat_load / flat_store / flat_atomic: instructions that count against BOTH the vector-
@@ -339,7 +338,6 @@ struct reina_engine {
     uint32_t day_flags = 0;                 // k_day's measurement switches (REINA_DAY_FLAGS), 0 in production
     bool export_by_copies = false;          // REINA_EXPORT=memcpy: reina_read_history by two copies even into page-locked memory (measurement handle)
     uint32_t exchange_words = REINA_PRESSURE_WORDS;   // int32 words of buffers.pressure a sharded population all-reduces per day
-    uint32_t cur_scan_waves = 0;            // waves of the day's k_day launch (set by the first half of a day for the second)
     uint32_t group_lds_rows = 0, group_lds_crows = 0;   // representative of a group: the most distinct contact / count rows any member holds (LDS sizing)
     uint32_t policy_lds_rows = 0, policy_lds_crows = 0;   // during a policy run (k_policy.inc): the most rows of any level of the bank -- the host does not know a member's level; 0 otherwise
     // (running independent kernels of a day on a second stream was measured on MI355X / ROCm 7.2:

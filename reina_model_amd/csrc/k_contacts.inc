@@ -19,7 +19,6 @@
 // Everything a contact decides is keyed by (source, day, contact number), so results do not depend on which
 // wave samples it, in which batch or in which order: bit-identical to oracle B's sequential loops.
 // k_day's launch flags (diagnostics and measurements; 0 in production)
-#define DAY_SPARSE_MIN_TILES 4u   // tiles per wave from which on a day is sparse (the launch decides: reina_hip.hip, day_is_sparse)
 // -DREINA_DAY_PROF (tools/day_prof.py): every wave sums the shader-clock cycles it spends in the parts of its loop; lane 0
 // adds them to buffers.mirror[32 + k] when the wave is through (k: 0 whole loop, 1 feed, 2 wait for fetched words, 3 wait for a
 // chunk of bits, 4 state-machine rounds, 5 contact batches, 6 of which resolve turns, 7 tail resolve; [48 + k]: counts)
@@ -32,8 +31,6 @@
 #define PROF_BEGIN(k) do { } while (0)
 #define PROF_END(k) do { } while (0)
 #endif
-#define DAY_THREADS 1024
-#define DAY_WAVES (DAY_THREADS / 64)
 #define NEEDY_ENTRIES 128                     // queued (agent, word) pairs: fewer than 64 carried over + at most 64 per feeding step
 #define DAY_XSTAGE (REINA_PRESSURE_WORDS / 2 - 1)   // exact attribution: contact records a workgroup stages in LDS (the pressure block's 8 KB: a count + 1023 records)
 

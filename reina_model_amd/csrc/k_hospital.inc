@@ -7,7 +7,6 @@
 // shuffle bitonic network up to 1024 events, a bucket sort above -- and the saturating bed / ICU walk is
 // replayed in that order as a workgroup scan; days with more events than LDS holds are walked in
 // priority ranges (hospital_block below).
-#define HOSP_THREADS 1024
 #define HOSP_SMALL_RANGES 32
 static_assert((uint64_t)HOSP_SMALL_RANGES * 65536u >= REINA_HOSP_SMALL_AGENTS, "REINA_HOSP_RANGES of a population walked by one workgroup");
 

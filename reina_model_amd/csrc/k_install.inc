@@ -320,7 +320,6 @@ __device__ __forceinline__ void install_block(const MemberRef &mref_, const rein
 // workgroup walks them in priority order (HI_HOSP_WG: workgroup 0, small populations) or the two launches
 // that follow do.  (A sharded population runs the same launches behind k_remote, which also takes the shard's
 // demand-proportional share of the pooled free beds / ICU units: the walk starts from that.)
-enum { HI_HOSP_WG = 1, HI_INSTALL = 2, HI_EVENTS = 4 };
 static_assert(HOSP_THREADS == 1024, "fused launch");
 // `n_walk`: the launch's first n_walk workgroups are the walkers of a large population's ordered day (k_hospital.inc:
 // hosp_walker_block); on any other day they install with the others.  Dynamic LDS: REINA_MAX_HOSP_EVENTS keys (HI_HOSP_WG) or

@@ -50,7 +50,6 @@ __global__ void k_init(const MemberRef *M_, int32_t beds, int32_t icu) {
 
 // ---------------------------------------------------------------------------------------------
 // k_prologue: single workgroup of 1024 threads.
-#define PRO_THREADS 1024
 #define PRO_MAX_IMPORTS 16384
 
 // Population.infect_people / get_import_infection_person (main.pyx:1632-1665), parallel form.
@@ -293,7 +292,6 @@ __device__ void pro_imports(const CAS DevParams *P, const GBuffers &B, const rei
 // agent added 1 to its age's counter by a global atomic -- neighbours in the index share their age, so a wave's 64 adds hit one
 // WORD and L2 takes them one by one, 12 ns each: 476 000 vaccinations a day at 10^8 agents were 6.8 ms, sixty times the rest of
 // the day; tools/vacc_probe.py.)
-#define VACC_CHUNKS 16
 struct VaccLds {
     uint32_t cnt[16 * VACC_CHUNKS], pre[16 * VACC_CHUNKS], tot[16 * VACC_CHUNKS / 64];
     int32_t hist[REINA_MAX_AGES], age_start[REINA_MAX_AGES + 1];
@@ -559,13 +557,6 @@ __device__ __forceinline__ void vacc_chain_programme(const CAS DevParams *P, con
     // (the words stay as they are: a workgroup in front may still be reading them; the next launch's tag is another, and a
     // new run starts from k_init's zeros)
 }
-// how the launch's workgroups are dealt to the day's programmes (reina_hip.hip).  `parallel`: the programmes' windows are
-// pairwise DISJOINT (age tiers side by side), so their order does not matter and every programme has workgroups of its own,
-// g[k] of them behind those of programmes 0 .. k - 1, all at once; otherwise all workgroups take the programmes one after the other.
-struct VaccGeom {
-    uint32_t parallel;
-    uint16_t g[REINA_MAX_VACCINATIONS];
-};
 __device__ __forceinline__ void pro_vaccinate_chain(const CAS DevParams *P, const GBuffers &B, const reina_day_t &dp, VaccLds &S, uint32_t b, uint32_t G,
                                                     uint32_t seq, const VaccGeom &geo) {
     vacc_begin(P, S);

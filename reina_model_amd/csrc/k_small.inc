@@ -61,7 +61,7 @@ __device__ __forceinline__ void small_day_barrier(GAS uint32_t *counter, uint32_
     __syncthreads();
 }
 
-// one day of the stretch: its descriptor and what the host decided about its launch shape (day_geometry)
+// one day of the stretch: its descriptor and what the host decided about its launch shape (reina_launch.h: plan_day)
 struct SmallDayRec {
     reina_day_t dp;
     int32_t weekly_own, mode;      // k_open's roles (k_testing.inc: open_role)

@@ -354,7 +354,6 @@ union OpenLds {
     OpenImportsLds imports;
     OpenTraceLds trace;
 };
-#define OPEN_WEEKLY_IN_STREAM 0x40000000
 template <bool X>
 __device__ __forceinline__ void open_role(const MemberRef &mref_, const reina_day_t &dp, uint32_t hist_slot, int weekly_own, int mode,
                                           uint32_t role, uint32_t n_roles, unsigned char *lds) {

@@ -65,13 +65,6 @@ enum { EV_HOSPITALIZE = 0, EV_TO_ICU = 1, EV_RELEASE_WARD = 2, EV_RELEASE_ICU = 
 // ---------------------------------------------------------------------------------------------
 // host side
 
-static int grid_for(uint32_t n_items, int threads, int max_blocks) {
-    long blocks = ((long)n_items + threads - 1) / threads;
-    if (blocks < 1) blocks = 1;
-    if (blocks > max_blocks) blocks = max_blocks;
-    return (int)blocks;
-}
-
 // HIP-event timing of the day's kernels (reina_profile_enable): start/stop timestamps ride on the kernel's
 // own dispatch packet (hipExtLaunchKernelGGL), no extra stream commands.  On a profiled day ONE kind of kernel
 // is timed (the kinds take turns), so the cost of timestamped dispatches is spread thinly over the run.
@@ -125,14 +118,21 @@ static bool kind_timed(int today, int kind) {
         }                                                                                                                \
     } while (0)
 
-// a kernel of the day: the GROUP instantiation for an engine group (members found in `refs`), else the single engine's
-// MemberRef by value (k_common.inc: DAY_KERNEL)
+// THE list of the day kernels' instantiations <GROUP, EXACT>: a single engine, a group's members (found in `refs`), a shard under
+// exact attribution (k_common.inc: DAY_KERNEL) -- k_day's each in the dense and the sparse form of the stream.  `f` is called
+// once per entry; what launches, sizes or checks the day kernels is written over these two.
+template <bool G, bool X, bool SP = false> struct DayForm { static constexpr bool group = G, exact = X, sparse = SP; };
+template <class F> static void each_day_form(F &&f) { f(DayForm<false, false>()); f(DayForm<true, false>()); f(DayForm<false, true>()); }
+template <class F> static void each_k_day_form(F &&f) {
+    each_day_form([&](auto m) { using M = decltype(m); f(DayForm<M::group, M::exact, false>()); f(DayForm<M::group, M::exact, true>()); });
+}
+// a kernel of the day: the instantiation of the launch's form -- K members, or the single engine's MemberRef by value
 #define LAUNCH_DAY(e, today, kind, kernel, grid, block, lds, stream, ...)                                                \
-    do {                                                                                                                 \
-        if (K > 1) LAUNCH_TIMED(e, today, kind, (kernel<true, false>), grid, block, lds, stream, refs, (e)->h_ref, __VA_ARGS__);  \
-        else if ((e)->exact) LAUNCH_TIMED(e, today, kind, (kernel<false, true>), grid, block, lds, stream, refs, (e)->h_ref, __VA_ARGS__); \
-        else LAUNCH_TIMED(e, today, kind, (kernel<false, false>), grid, block, lds, stream, refs, (e)->h_ref, __VA_ARGS__); \
-    } while (0)
+    each_day_form([&](auto m_) {                                                                                         \
+        using M_ = decltype(m_);                                                                                         \
+        if (M_::group == (K > 1) && M_::exact == (K == 1 && (e)->exact))                                                 \
+            LAUNCH_TIMED(e, today, kind, (kernel<M_::group, M_::exact>), grid, block, lds, stream, refs, (e)->h_ref, __VA_ARGS__); \
+    })
 
 static void resolve_profile(reina_engine *e) {
     for (int k = 0; k < REINA_PK_NR; k++) {
@@ -206,6 +206,20 @@ static void count_row_for(float nr_contacts, uint32_t *thr, uint8_t *guide) {
     if (rows.size() < 4096) rows.emplace(key, row);
 }
 
+// the environment's switches (read in reina_create): a flag, or a number that counts only within [lo, hi]
+static void env_flag(const char *name, bool *v) {
+    if (const char *w = std::getenv(name)) *v = std::atoi(w) != 0;
+}
+static void env_uint(const char *name, int lo, int hi, uint32_t *v) {
+    const char *w = std::getenv(name);
+    if (w && std::atoi(w) >= lo && std::atoi(w) <= hi) *v = (uint32_t)std::atoi(w);
+}
+// reina_create's way out of a configuration it refuses
+static int refuse_create(reina_engine *e, const std::string &text, int code = REINA_E_INVALID) {
+    free_engine(e);
+    return refuse(text, code);
+}
+
 extern "C" {
 
 int reina_abi_version(void) { return 7; }
@@ -276,22 +290,13 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 1)
             e->n_cus = (uint32_t)cus;
-        if (const char *w = std::getenv("REINA_VACC_ONE_WG")) e->vacc_one_wg = std::atoi(w) != 0;   // (the single-workgroup vaccination pass at every size: the tests compare)
-        if (const char *w = std::getenv("REINA_NO_PLACE_GROUPS")) e->no_place_groups = std::atoi(w) != 0;
-        if (const char *w = std::getenv("REINA_LDS_ROWS_CAP")) {
-            const int v = std::atoi(w);
-            if (v >= 1) e->lds_rows_cap = (uint32_t)v;
-        }
-        if (const char *w = std::getenv("REINA_WALK_DIV")) {
-            const int v = std::atoi(w);
-            if (v >= 16 && v <= 1024) e->walk_div = (uint32_t)v;
-        }
-        if (const char *w = std::getenv("REINA_IMPORT_WGS")) {
-            const int v = std::atoi(w);
-            if (v >= 1 && v <= 16) e->import_wgs = (uint32_t)v;
-        }
+        env_flag("REINA_VACC_ONE_WG", &e->vacc_one_wg);   // (the single-workgroup vaccination pass at every size: the tests compare)
+        env_flag("REINA_NO_PLACE_GROUPS", &e->no_place_groups);
+        env_uint("REINA_LDS_ROWS_CAP", 1, INT_MAX, &e->lds_rows_cap);
+        env_uint("REINA_WALK_DIV", 16, 1024, &e->walk_div);
+        env_uint("REINA_IMPORT_WGS", 1, 16, &e->import_wgs);
         // k_day streams the ACTIVE bit plane instead of the hot words when the population is large enough for that form to pay
-        // (day_is_sparse).  REINA_DAY_MODE = dense | sparse forces one form whatever the size (the tests run every scenario in
+        // (reina_launch.h: plan_day).  REINA_DAY_MODE = dense | sparse forces one form whatever the size (the tests run every scenario in
         // both), alternate switches between them day by day; REINA_DAY_FLAGS are k_day's measurement switches
         if (const char *w = std::getenv("REINA_DAY_MODE")) {
             if (!std::strcmp(w, "dense")) e->day_mode = 1;
@@ -300,16 +305,13 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
         }
         if (const char *w = std::getenv("REINA_DAY_FLAGS")) e->day_flags |= (uint32_t)std::atoi(w);
         if (const char *w = std::getenv("REINA_EXPORT")) e->export_by_copies = !std::strcmp(w, "memcpy");
-        if (const char *w = std::getenv("REINA_OPEN_TICKETS")) e->open_tickets = std::atoi(w) != 0;   // (the tests' handle on the ticket path of a single engine)
-        if (const char *w = std::getenv("REINA_IMPORTS_IN_OPEN")) e->imports_in_open = std::atoi(w) != 0;   // (the round-3 placement, for comparison)
+        env_flag("REINA_OPEN_TICKETS", &e->open_tickets);   // (the tests' handle on the ticket path of a single engine)
+        env_flag("REINA_IMPORTS_IN_OPEN", &e->imports_in_open);   // (the round-3 placement, for comparison)
         // stretches of days of a small unsharded population as ONE launch (k_small.inc): REINA_FUSED_DAY=1 switches it on (off by
         // default: measured slower than the three launches a day; the tests run scenario families both ways), REINA_FUSED_WGS its
         // workgroups (measurement handle; 8..64)
-        if (const char *w = std::getenv("REINA_FUSED_DAY")) e->fused_day = std::atoi(w) != 0;
-        if (const char *w = std::getenv("REINA_FUSED_WGS")) {
-            const int v = std::atoi(w);
-            if (v >= 8 && v <= 64) e->small_wgs = (uint32_t)v;
-        }
+        env_flag("REINA_FUSED_DAY", &e->fused_day);
+        env_uint("REINA_FUSED_WGS", 8, 64, &e->small_wgs);
     }
     std::memset(&e->h_params, 0, sizeof(DevParams));
     std::memset(&e->h_tables, 0, sizeof(Tables));
@@ -319,10 +321,8 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
     e->h_params.nr_ages = cfg->nr_ages;
     e->h_params.nr_variants = cfg->nr_variants;
     e->cfg.n_shards = cfg->n_shards ? cfg->n_shards : 1;
-    if (e->cfg.n_shards > REINA_MAX_SHARDS || e->cfg.shard_rank >= e->cfg.n_shards) {
-        delete e;
-        return refuse("n_shards / shard_rank out of range");
-    }
+    if (e->cfg.n_shards > REINA_MAX_SHARDS || e->cfg.shard_rank >= e->cfg.n_shards)
+        return refuse_create(e, "n_shards / shard_rank out of range");
     const uint64_t shard_seed = rp_shard_seed(cfg->seed, e->cfg.shard_rank);
     e->h_params.k0 = (uint32_t)shard_seed;
     e->h_params.k1 = (uint32_t)(shard_seed >> 32);
@@ -335,10 +335,8 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
     e->h_params.n_shards = e->cfg.n_shards;
     e->h_params.shard_rank = e->cfg.shard_rank;
     e->h_params.mirror_slots = cfg->mirror_slots ? cfg->mirror_slots : 64;
-    if (e->h_params.mirror_slots & (e->h_params.mirror_slots - 1)) {
-        delete e;
-        return refuse("mirror_slots must be a power of two");
-    }
+    if (e->h_params.mirror_slots & (e->h_params.mirror_slots - 1))
+        return refuse_create(e, "mirror_slots must be a power of two");
     for (uint32_t v = 0; v < cfg->nr_variants; v++) {
         float m = 0.0f;
         for (uint32_t a = 0; a < cfg->nr_ages; a++)
@@ -349,10 +347,8 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
     e->exact = cfg->exact_attribution != 0 && e->cfg.n_shards > 1;
     e->h_params.gid_mask = 0xFFFFFFFFu;
     if (e->exact) {
-        if (!cfg->shard_age_start || cfg->xchg_cap == 0 || cfg->pool_cap == 0 || cfg->n_agents > RP_GID_INDEX_MASK) {
-            delete e;
-            return refuse("exact attribution needs shard_age_start, xchg_cap > 0, pool_cap > 0 and fewer than 2^27 agents per shard");
-        }
+        if (!cfg->shard_age_start || cfg->xchg_cap == 0 || cfg->pool_cap == 0 || cfg->n_agents > RP_GID_INDEX_MASK)
+            return refuse_create(e, "exact attribution needs shard_age_start, xchg_cap > 0, pool_cap > 0 and fewer than 2^27 agents per shard");
         e->h_params.exact = 1u;
         e->h_params.gid_base = e->cfg.shard_rank << RP_GID_SHIFT;
         e->h_params.gid_mask = RP_GID_INDEX_MASK;
@@ -380,21 +376,17 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
     e->h_params.max_hosp_events = cfg->max_hosp_events > REINA_MAX_HOSP_EVENTS ? cfg->max_hosp_events : REINA_MAX_HOSP_EVENTS;
     e->h_params.hosp_ranges = cfg->hosp_ranges ? cfg->hosp_ranges : REINA_HOSP_RANGES(cfg->n_agents);
     e->h_params.xchg_stride = (uint32_t)REINA_XCHG_SEG_WORDS(e->h_params.xchg_cap, e->h_params.hosp_ranges);   // (exact attribution: a segment = count + records + trailer)
-    if (e->h_params.hosp_ranges < 16 || e->h_params.hosp_ranges > REINA_HOSP_MAX_RANGES || (e->h_params.hosp_ranges & (e->h_params.hosp_ranges - 1))) {
-        delete e;
-        return refuse("hosp_ranges must be a power of two in [16, REINA_HOSP_MAX_RANGES]");
-    }
+    if (e->h_params.hosp_ranges < 16 || e->h_params.hosp_ranges > REINA_HOSP_MAX_RANGES || (e->h_params.hosp_ranges & (e->h_params.hosp_ranges - 1)))
+        return refuse_create(e, "hosp_ranges must be a power of two in [16, REINA_HOSP_MAX_RANGES]");
     e->h_params.hosp_range_bits = 0;
     while ((1u << e->h_params.hosp_range_bits) < e->h_params.hosp_ranges) e->h_params.hosp_range_bits++;
     e->h_params.hosp_bucket_cap = REINA_HOSP_BUCKET_CAP_R(e->h_params.hosp_ranges, cfg->max_hosp_events);
     // (a sharded population always takes the bucket-per-wave walk: its shards exchange per-bucket maps)
     e->h_params.hosp_parallel = (cfg->n_agents > REINA_HOSP_SMALL_AGENTS || e->cfg.n_shards > 1) ? 1u : 0u;
     e->exchange_words = (uint32_t)REINA_EXCHANGE_WORDS(e->cfg.n_shards, e->h_params.hosp_ranges);
-    if (e->h_params.hosp_parallel && e->h_params.hosp_bucket_cap > REINA_HOSP_MAX_BUCKET_KEYS) {
-        delete e;
-        return refuse("max_hosp_events too large for this population: a bucket of the event walk holds at most 4096 keys "
+    if (e->h_params.hosp_parallel && e->h_params.hosp_bucket_cap > REINA_HOSP_MAX_BUCKET_KEYS)
+        return refuse_create(e, "max_hosp_events too large for this population: a bucket of the event walk holds at most 4096 keys "
                       "(pass at most REINA_HOSP_MAX_EVENTS_FOR(n_agents), include/reina_hip.h)");
-    }
     HIP_CHECK_OR(hipMalloc(&e->d_params, sizeof(DevParams)), free_engine(e));
     HIP_CHECK_OR(hipMalloc(&e->d_tables, sizeof(Tables)), free_engine(e));
     HIP_CHECK_OR(hipMalloc(&e->d_ref, sizeof(MemberRef)), free_engine(e));
@@ -404,38 +396,33 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
     // sized for the larger of its launch shapes)
     const size_t walk_lds = (size_t)HOSP_P_THREADS * HOSP_P_E * 8, small_lds = (size_t)REINA_MAX_HOSP_EVENTS * 8;
     const int day_lds = (int)day_shared_bytes(REINA_LDS_ROWS, REINA_LDS_CROWS, REINA_MAX_SHARDS), inst_lds = (int)(walk_lds > small_lds ? walk_lds : small_lds);
-#define SET_LDS(kernel, bytes)                                                                                                                       \
-    HIP_CHECK_OR(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes), free_engine(e)); \
-    HIP_CHECK_OR(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes), free_engine(e));  \
-    HIP_CHECK_OR(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes), free_engine(e))
-#define SET_LDS_DAY(SP)                                                                                                                              \
-    HIP_CHECK_OR(hipFuncSetAttribute(reinterpret_cast<const void *>(k_day<false, false, SP>), hipFuncAttributeMaxDynamicSharedMemorySize, day_lds), free_engine(e)); \
-    HIP_CHECK_OR(hipFuncSetAttribute(reinterpret_cast<const void *>(k_day<true, false, SP>), hipFuncAttributeMaxDynamicSharedMemorySize, day_lds), free_engine(e));  \
-    HIP_CHECK_OR(hipFuncSetAttribute(reinterpret_cast<const void *>(k_day<false, true, SP>), hipFuncAttributeMaxDynamicSharedMemorySize, day_lds), free_engine(e))
-    SET_LDS_DAY(false);
-    SET_LDS_DAY(true);
-#undef SET_LDS_DAY
-    {
-        // k_day addresses v104..v127 by hand (k_contacts.inc): the code object must allocate all 128 registers to every instantiation.
-        // tests/test_abi.py checks that in the disassembly of the build it runs on; this is the check a box without the tests makes
-        // (round-5 verdict: a compiler that stopped honouring the clobber list would hand the kernel fewer registers than it names)
-        const void *day_kernels[6] = {reinterpret_cast<const void *>(k_day<false, false, false>), reinterpret_cast<const void *>(k_day<false, false, true>),
-                                      reinterpret_cast<const void *>(k_day<true, false, false>), reinterpret_cast<const void *>(k_day<true, false, true>),
-                                      reinterpret_cast<const void *>(k_day<false, true, false>), reinterpret_cast<const void *>(k_day<false, true, true>)};
-        for (const void *k : day_kernels) {
-            hipFuncAttributes fa;
-            HIP_CHECK_OR(hipFuncGetAttributes(&fa, k), free_engine(e));
-            if (fa.numRegs != 128 || fa.localSizeBytes != 0) {
-                free_engine(e);
-                return refuse("k_day was built with " + std::to_string(fa.numRegs) + " VGPRs / " + std::to_string(fa.localSizeBytes) +
-                                  " bytes of scratch: it names v104..v127 by hand and needs 128 / 0 (rebuild with the ROCm release the sources were written for)",
-                              REINA_E_HIP);
-            }
-        }
-    }
-    SET_LDS(k_hosp_presort, (int)walk_lds);
-    SET_LDS(k_hosp_install, inst_lds);
-#undef SET_LDS
+    hipError_t lds_err = hipSuccess;
+    auto set_lds = [&](const void *kernel, int bytes) {
+        if (lds_err == hipSuccess) lds_err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    };
+    // k_day addresses v104..v127 by hand (k_contacts.inc): the code object must allocate all 128 registers to every instantiation.
+    // tests/test_abi.py checks that in the disassembly of the build it runs on; this is the check a box without the tests makes
+    // (round-5 verdict: a compiler that stopped honouring the clobber list would hand the kernel fewer registers than it names)
+    hipFuncAttributes bad;
+    bad.numRegs = 128, bad.localSizeBytes = 0;
+    each_k_day_form([&](auto m) {
+        using M = decltype(m);
+        const void *kernel = reinterpret_cast<const void *>(k_day<M::group, M::exact, M::sparse>);
+        set_lds(kernel, day_lds);
+        hipFuncAttributes fa;
+        if (lds_err == hipSuccess) lds_err = hipFuncGetAttributes(&fa, kernel);
+        if (lds_err == hipSuccess && (fa.numRegs != 128 || fa.localSizeBytes != 0)) bad = fa;
+    });
+    each_day_form([&](auto m) {
+        using M = decltype(m);
+        set_lds(reinterpret_cast<const void *>(k_hosp_presort<M::group, M::exact>), (int)walk_lds);
+        set_lds(reinterpret_cast<const void *>(k_hosp_install<M::group, M::exact>), inst_lds);
+    });
+    HIP_CHECK_OR(lds_err, free_engine(e));
+    if (bad.numRegs != 128 || bad.localSizeBytes != 0)
+        return refuse_create(e, "k_day was built with " + std::to_string(bad.numRegs) + " VGPRs / " + std::to_string(bad.localSizeBytes) +
+                                    " bytes of scratch: it names v104..v127 by hand and needs 128 / 0 (rebuild with the ROCm release the sources were written for)",
+                             REINA_E_HIP);
     {
         // the fused day of a small population: its LDS block (the stream's image or the hospital role's keys + maps, whichever is
         // larger) beside the static LDS of the three phases' functions must fit one compute unit; its barrier counter
@@ -649,263 +636,83 @@ int reina_upload_contact_tables(reina_engine_t *e, const reina_contact_tables_t 
     return stage_upload(e, e->h_params, e->h_tables, e->d_params, e->d_tables, (hipStream_t)stream);
 }
 
-// k_day's workgroups for one engine instance: one 512-agent tile per wave (small populations) up to one
-// workgroup of 16 waves per CU, whose waves then walk several tiles; members of a group share the chip.
-// Every later kernel takes the resulting wave count as a parameter (the per-wave slices of the lists).
-static uint32_t day_blocks_for(uint32_t n_agents, uint32_t K, uint32_t n_cus) {
-    const uint32_t tiles = ((n_agents >> 2) + 127u) / 128u;
-    uint32_t b = (tiles + DAY_WAVES - 1) / DAY_WAVES;
-    if (b < 1) b = 1;
-    uint32_t cap = K > 1 ? (n_cus / K > 0 ? n_cus / K : 1u) : n_cus;
-    if (cap > REINA_MAX_SCAN_WAVES / DAY_WAVES) cap = REINA_MAX_SCAN_WAVES / DAY_WAVES;
-    if (b > cap) b = cap;
-    return b;
-}
-
-// One day's launches for K engine instances at once (K = 1: a single engine; K > 1: a group of
-// identically configured engines, one launch per phase for all of them, member = blockIdx.y).
-// `e` is the representative engine: geometry, scenario flags, optional second stream.
+// One day's launches for K engine instances at once (K = 1: a single engine; K > 1: a group of identically configured
+// engines, one launch per phase for all of them, member = blockIdx.y), `e` the representative engine.  What is launched, and
+// how large, is the day's PLAN (reina_launch.h: plan_day, a pure function): planned once a day by reina_step_day and
+// group_run_days, on every call by the stateless entry points; the launchers below only launch.
 // The day comes in the PHASES of include/reina_hip.h (reina_step_phase): between them a sharded population exchanges.
-struct DayGeom {   // what the launches of a day's first phases agree on (a function of the engine and the day alone)
-    int weekly_own;            // k_open's import roles (k_testing.inc: open_role)
-    uint32_t stream_imports;   // workgroups of k_day's launch that place the weekly imports beside the stream
-    uint32_t day_blocks;       // streaming workgroups of k_day
-    bool xtrace;               // exact attribution on a contact-tracing day: tracing level by level, an exchange behind each
-};
-static int day_geometry(reina_engine_t *e, uint32_t K, const reina_day_t &dp, DayGeom *g) {
-    const uint32_t N = e->cfg.n_agents;
-    if (dp.day >= REINA_MAX_DAYS) {
-        // claim / mirror keys carry the day in 12 bits (rp_order_key) and claim[] is never cleared: from day
-        // 4096 on, stale claims would beat today's
-        return refuse("day >= REINA_MAX_DAYS (4096): the winner-selection keys carry the day in 12 bits");
-    }
-    if (dp.n_import_batches > REINA_MAX_IMPORT_BATCHES || dp.n_vaccinations > REINA_MAX_VACCINATIONS) return refuse("n_import_batches / n_vaccinations out of range");
+static LaunchShape launch_shape(const reina_engine_t *e) {
+    return LaunchShape{e->cfg.n_agents, e->n_cus, e->cfg.n_shards, e->exact, e->h_params.hosp_ranges, e->h_params.hosp_parallel,
+                       e->h_params.cand_ovf_cap, e->cfg.max_work_items, e->cfg.xchg_cap, e->import_wgs, e->walk_div, e->vacc_one_wg,
+                       e->open_tickets, e->imports_in_open, (uint32_t)e->day_mode, e->lds_rows_cap, e->small_wgs};
+}
+// THE step that notes that a population has ever tested (k_open's test-queue roles run from then on): the caller's, before it plans
+static void note_testing(reina_engine_t *e, const reina_day_t &dp) {
     if (dp.testing_mode != RT_NO_TESTING) e->testing_ever = true;
-    uint32_t n_pre = 0, n_post = 0;
-    for (uint32_t b = 0; b < dp.n_import_batches; b++)
-        (dp.import_batches[b].pre_init ? n_pre : n_post) += dp.import_batches[b].count;
-    // weekly imports on a day without intervention imports (which would share their claim keys) have workgroups of their
-    // own: one per wave of imports, at most 16 (k_open.inc, imports_any); members of a group take one each (they wait on each
-    // other, and a group's launch is not resident as a whole)
-    // (> 0: so many workgroups for the weekly imports; <= 0: the opening workgroup places the day's imports, with -weekly_own
-    // helpers: open_role, k_testing.inc)
-    int weekly_own = n_pre == 0 && n_post > 0;
-    if (K == 1) {
-        const uint32_t most = n_pre > n_post ? n_pre : n_post;
-        int w = (int)((most + 511u) / 512u);
-        if (w > (int)e->import_wgs) w = (int)e->import_wgs;
-        if (weekly_own) weekly_own = w;
-        else if (n_pre > 0 && w > 1) weekly_own = -(w - 1);
+}
+static int plan_engine_day(const reina_engine_t *e, uint32_t K, const reina_day_t &dp, DayPlan *plan) {
+    uint32_t rows = K > 1 ? e->group_lds_rows : e->h_tables.n_rows, crows = K > 1 ? e->group_lds_crows : e->h_tables.n_crows;   // (a member stages min(its own rows, lds_rows))
+    if (e->policy_lds_rows) rows = e->policy_lds_rows;   // (a policy run: the most rows of any level of its bank, k_policy.inc)
+    if (e->policy_lds_crows) crows = e->policy_lds_crows;
+    switch (plan_day(launch_shape(e), K, e->testing_ever, rows, crows, dp, plan)) {
+    case PLAN_E_DAY: return refuse("day >= REINA_MAX_DAYS (4096): the winner-selection keys carry the day in 12 bits");
+    case PLAN_E_COUNTS: return refuse("n_import_batches / n_vaccinations out of range");
     }
-    uint32_t day_blocks = day_blocks_for(N, K, e->n_cus);
-    // weekly imports on a day without intervention imports are placed in k_day's launch, beside the stream, by workgroups
-    // of their own behind the streaming ones (k_open.inc: deferred placement); all of them fit the chip together.
-    // (Their records go to the shared candidate overflow list: only when the day's imports fit it with room to spare for real
-    // overflow records -- a caller of the C ABI may have sized max_candidates tightly -- else the opening launch places them)
-    uint32_t stream_imports = 0;
-    if (weekly_own > 0 && dp.day + 1u < REINA_MAX_DAYS && !e->imports_in_open && (uint64_t)n_post * 2u <= e->h_params.cand_ovf_cap) {
-        stream_imports = K == 1 ? (uint32_t)weekly_own : 1u;
-        const uint32_t cap = K > 1 ? (e->n_cus / K > 0 ? e->n_cus / K : 1u) : e->n_cus;
-        if (day_blocks + stream_imports > cap && cap > stream_imports) day_blocks = cap - stream_imports;
-        weekly_own = OPEN_WEEKLY_IN_STREAM;
-    }
-    g->weekly_own = weekly_own;
-    g->stream_imports = stream_imports;
-    g->day_blocks = day_blocks;
-    g->xtrace = e->exact && dp.testing_mode == RT_ALL_WITH_SYMPTOMS_CT;
     return REINA_OK;
 }
 
 // REINA_PH_OPEN: the day's opening -- roles (0 opens the day, 1 weekly imports, 2.. the test queue) by arrival ticket
-static int launch_day_open(reina_engine_t *e, const MemberRef *refs, uint32_t K, const reina_day_t &dp, uint32_t hist_slot, hipStream_t s) {
-    DayGeom geo;
-    if (int rc = day_geometry(e, K, dp, &geo)) return rc;
-    const uint32_t N = e->cfg.n_agents;
+static void launch_day_open(reina_engine_t *e, const MemberRef *refs, uint32_t K, const reina_day_t &dp, const DayPlan &p, uint32_t hist_slot, hipStream_t s) {
     const int today = profiled_kind(e, dp.day);
-    const int weekly_own = geo.weekly_own;
-    // (groups: the members share the chip, so each gets proportionally fewer workgroups per phase)
-    int tg = grid_for(N / 64 + 1, PRO_THREADS, 64);
-    if (K > 1 && tg > (int)(e->n_cus / K)) tg = e->n_cus / K > 0 ? (int)(e->n_cus / K) : 1;
-    const bool ct = dp.testing_mode == RT_ALL_WITH_SYMPTOMS_CT;
-    const int helpers = weekly_own == OPEN_WEEKLY_IN_STREAM ? 0 : weekly_own > 0 ? weekly_own : -weekly_own;
-    const int g0 = 1 + (helpers > 1 ? helpers : 1), g = g0 + tg;
-    // roles by arrival ticket unless the launch is resident as a whole -- and, measured, for small populations too
-    // (HUS year: k_open 10.4 us a day with tickets, 11.2 by block number; 10^8 agents: 14.6 against 14.1)
-    const int open_tickets = (K > 1 || g > (int)e->n_cus || e->open_tickets || N <= 8000000u) ? 1 : 0;
-    if (!e->testing_ever) {
-        LAUNCH_DAY(e, today, REINA_PK_OPEN, k_open, dim3(g0, K), dim3(PRO_THREADS), 0, s, dp, hist_slot, weekly_own, 0, open_tickets);
-    } else if (ct && N <= 8000000u && !geo.xtrace) {
-        LAUNCH_DAY(e, today, REINA_PK_OPEN, k_open, dim3(g, K), dim3(PRO_THREADS), 0, s, dp, hist_slot, weekly_own, 3, open_tickets);  // detects + traces, both levels
-    } else if (ct) {
-        // detects + traces level 0; level 1 by a launch of its own (exact attribution: behind the exchange of the level-0 requests)
-        LAUNCH_DAY(e, today, REINA_PK_OPEN, k_open, dim3(g, K), dim3(PRO_THREADS), 0, s, dp, hist_slot, weekly_own, 2, open_tickets);
-        if (!geo.xtrace) LAUNCH_DAY(e, today, REINA_PK_TRACE1, k_test_trace1, dim3(grid_for(N / 64 + 1, 256, 256), K), dim3(256), 0, s, dp);
-    } else {
-        LAUNCH_DAY(e, today, REINA_PK_OPEN, k_open, dim3(g, K), dim3(PRO_THREADS), 0, s, dp, hist_slot, weekly_own, 1, open_tickets);
-    }
-    HIP_CHECK(hipGetLastError());
-    return REINA_OK;
+    LAUNCH_DAY(e, today, REINA_PK_OPEN, k_open, dim3(p.open_grid, K), dim3(PRO_THREADS), 0, s, dp, hist_slot, p.weekly_own, (int)p.open_mode, (int)p.open_tickets);
+    if (p.trace1_in_open) LAUNCH_DAY(e, today, REINA_PK_TRACE1, k_test_trace1, dim3(p.trace1_grid, K), dim3(256), 0, s, dp);
 }
-
-// workgroups of a launch that takes in the records of an exchange (k_xtrace, k_feedback)
-static int xchg_grid(const reina_engine_t *e) { return grid_for(e->cfg.xchg_cap * (e->cfg.n_shards - 1u) / 4u + 1u, 256, 128); }
-
 // REINA_PH_TRACE (exact attribution, contact-tracing days): the level-0 requests of the other shards, then level 1
-static int launch_day_trace(reina_engine_t *e, const MemberRef *refs, uint32_t K, const reina_day_t &dp, hipStream_t s) {
-    DayGeom geo;
-    if (int rc = day_geometry(e, K, dp, &geo)) return rc;
-    if (!geo.xtrace) return REINA_OK;
+static void launch_day_trace(reina_engine_t *e, const MemberRef *refs, uint32_t K, const reina_day_t &dp, const DayPlan &p, hipStream_t s) {
+    if (!p.xtrace) return;
     const int today = profiled_kind(e, dp.day);
-    LAUNCH_DAY(e, today, REINA_PK_XCHG, k_xtrace, dim3(xchg_grid(e), K), dim3(256), 0, s, dp, 0);
-    LAUNCH_DAY(e, today, REINA_PK_TRACE1, k_test_trace1, dim3(grid_for(e->cfg.n_agents / 64 + 1, 256, 256), K), dim3(256), 0, s, dp);
-    HIP_CHECK(hipGetLastError());
-    return REINA_OK;
+    LAUNCH_DAY(e, today, REINA_PK_XCHG, k_xtrace, dim3(p.xchg_grid, K), dim3(256), 0, s, dp, 0);
+    LAUNCH_DAY(e, today, REINA_PK_TRACE1, k_test_trace1, dim3(p.trace1_grid, K), dim3(256), 0, s, dp);
 }
-
-// REINA_PH_MAIN: (the level-1 requests of the other shards,) vaccination, the stream with the contact sampling, and a sharded
+// REINA_PH_MAIN: (the level-1 requests of the other shards,) vaccination -- its pass over the agents comes after the test queue and
+// before the stream (HealthcareSystem.iterate, main.pyx:514-558) --, the stream with the contact sampling, and a sharded
 // population's event maps for the all-reduce
-static int launch_day_main(reina_engine_t *e, const MemberRef *refs, uint32_t K, const reina_day_t &dp, hipStream_t s) {
-    DayGeom geo;
-    if (int rc = day_geometry(e, K, dp, &geo)) return rc;
+static void launch_day_main(reina_engine_t *e, const MemberRef *refs, uint32_t K, const reina_day_t &dp, const DayPlan &p, hipStream_t s) {
     const int today = profiled_kind(e, dp.day);
-    if (geo.xtrace) LAUNCH_DAY(e, today, REINA_PK_XCHG, k_xtrace, dim3(xchg_grid(e), K), dim3(256), 0, s, dp, 1);
-    const uint32_t day_blocks = geo.day_blocks, stream_imports = geo.stream_imports;
-    uint32_t lds_rows = K > 1 ? e->group_lds_rows : e->h_tables.n_rows;   // (a member stages min(its own rows, lds_rows))
-    if (e->policy_lds_rows) lds_rows = e->policy_lds_rows;   // (a policy run: the most rows of any level of its bank, k_policy.inc)
-    if (lds_rows > REINA_LDS_ROWS) lds_rows = REINA_LDS_ROWS;
-    if (e->lds_rows_cap && lds_rows > e->lds_rows_cap) lds_rows = e->lds_rows_cap;
-    uint32_t lds_crows = K > 1 ? e->group_lds_crows : e->h_tables.n_crows;
-    if (e->policy_lds_crows) lds_crows = e->policy_lds_crows;
-    if (lds_crows > REINA_LDS_CROWS) lds_crows = REINA_LDS_CROWS;
-    if (e->lds_rows_cap && lds_crows > e->lds_rows_cap) lds_crows = e->lds_rows_cap;
-    // a vaccination programme: its pass over the agents comes after the test queue and before the stream
-    // (HealthcareSystem.iterate, main.pyx:514-558)
-    if (dp.n_vaccinations) {
-        // a day on which some programme's number exceeds a step of 16 x 1024 agents: a chain of workgroups, one step each, with room
-        // for a third more agents than the largest number (k_open.inc: pro_vaccinate_chain; the programmes one after the other, the
-        // launch agreeing on each one's end); otherwise one workgroup.  (the numbers as the kernel clips them: a programme whose window
-        // holds fewer agents never needs the chain.)  Members of a group chain too while the whole launch stays resident.
-        uint32_t vg = 1, most = 0, need[REINA_MAX_VACCINATIONS], sum_need = 0;
-        bool disjoint = dp.n_vaccinations > 1;
-        for (uint32_t k = 0; k < dp.n_vaccinations; k++) {
-            const reina_vaccination_t &vk = dp.vaccinations[k];
-            const uint32_t window = vk.idx_end > vk.idx_start ? vk.idx_end - vk.idx_start : 0u;
-            const uint32_t nrk = vk.nr < window ? vk.nr : window;
-            if (nrk > most) most = nrk;
-            need[k] = (nrk + nrk / 3u) / (VACC_CHUNKS * PRO_THREADS) + 1u;
-            sum_need += need[k];
-            for (uint32_t j = 0; j < k; j++)
-                if (vk.idx_start < dp.vaccinations[j].idx_end && dp.vaccinations[j].idx_start < vk.idx_end) disjoint = false;
-        }
-        VaccGeom geo;
-        std::memset(&geo, 0, sizeof(geo));
-        // (the published words live in the head of buffers.scan_lists: 16 programmes x 512 + 16 arrival words, 64 bits each)
-        if (most > VACC_CHUNKS * PRO_THREADS && e->cfg.max_work_items >= 8192 + 16 && !e->vacc_one_wg) {
-            uint32_t cap = K > 1 ? e->n_cus / K : e->n_cus;
-            if (cap > 256u) cap = 256u;
-            if (disjoint && sum_need <= cap) {
-                // age tiers side by side (windows pairwise disjoint: the order of the programmes does not matter): every
-                // programme on workgroups of its own, all at once
-                geo.parallel = 1u;
-                for (uint32_t k = 0; k < dp.n_vaccinations; k++) geo.g[k] = (uint16_t)need[k];
-                vg = sum_need;
-            } else {
-                vg = (most + most / 3u) / (VACC_CHUNKS * PRO_THREADS) + 1u;
-                if (vg > cap) vg = cap;
-            }
-            if (vg < 1u) vg = 1u;
-        }
+    if (p.xtrace) LAUNCH_DAY(e, today, REINA_PK_XCHG, k_xtrace, dim3(p.xchg_grid, K), dim3(256), 0, s, dp, 1);
+    if (p.vacc_grid) {
         // The tag is drawn from ONE process-wide counter (round-5 advisor): the tagged words live in each member's own buffers and
         // are never cleared, so a per-engine counter could come back to a value those buffers already hold -- a member stepped in
         // a group (tag = the representative's count) and later alone or under another representative.  A process-wide value is
         // never reused on any buffers (2^32 - 1 vaccination launches per process before it wraps).
         static std::atomic<uint32_t> vacc_seq_next{0};
         do e->vacc_seq = ++vacc_seq_next; while (e->vacc_seq == 0u);
-        LAUNCH_DAY(e, today, REINA_PK_VACCINATE, k_vaccinate, dim3(vg, K), dim3(PRO_THREADS), 0, s, dp, e->vacc_seq, geo);
+        LAUNCH_DAY(e, today, REINA_PK_VACCINATE, k_vaccinate, dim3(p.vacc_grid, K), dim3(PRO_THREADS), 0, s, dp, e->vacc_seq, p.vacc);
     }
-    {
-        // the form of the stream (k_contacts.inc): sparse from DAY_SPARSE_MIN_TILES tiles per wave on -- every day of such a population:
-        // a threshold on yesterday's active agents (rounds 4-5, decided in the kernel) never chose the dense form where the sparse
-        // one was possible
-        const uint32_t tiles = ((e->cfg.n_agents >> 2) + 127u) / 128u;
-        bool sparse = e->day_mode == 2 || (e->day_mode == 0 && tiles >= DAY_SPARSE_MIN_TILES * day_blocks * DAY_WAVES);
-        if (e->day_mode == 3) sparse = (dp.day & 1u) == 0u;
-        const dim3 grid(day_blocks + stream_imports, K), block(DAY_THREADS);
-        const size_t lds = day_shared_bytes(lds_rows, lds_crows, e->cfg.n_shards);
-#define K_DAY(G, X, SP) LAUNCH_TIMED(e, today, REINA_PK_DAY, (k_day<G, X, SP>), grid, block, lds, s, refs, (e)->h_ref, dp, lds_rows, lds_crows, e->day_flags, stream_imports)
-        if (K > 1) { if (sparse) K_DAY(true, false, true); else K_DAY(true, false, false); }
-        else if (e->exact) { if (sparse) K_DAY(false, true, true); else K_DAY(false, true, false); }
-        else { if (sparse) K_DAY(false, false, true); else K_DAY(false, false, false); }
-#undef K_DAY
-    }
-    e->cur_scan_waves = day_blocks * DAY_WAVES;   // (the day's later launches walk the per-wave slices)
-    if (e->cfg.n_shards > 1) {
-        // a sharded population: its event buckets sorted and their maps written to the exchange block BEFORE the all-reduce
-        const uint32_t n_walk = (e->h_params.hosp_ranges + 15u) / 16u;
-        LAUNCH_DAY(e, today, REINA_PK_HOSP_SORT, k_hosp_presort, dim3(n_walk, K), dim3(HOSP_THREADS), (size_t)HOSP_P_THREADS * HOSP_P_E * 8, s, dp);
-    }
-    HIP_CHECK(hipGetLastError());
-    return REINA_OK;
+    const dim3 grid(p.day_blocks + p.stream_imports, K);
+    const size_t lds = day_shared_bytes(p.lds_rows, p.lds_crows, e->cfg.n_shards);
+    each_k_day_form([&](auto m) {
+        using M = decltype(m);
+        if (M::group == (K > 1) && M::exact == (K == 1 && e->exact) && M::sparse == (p.sparse != 0u))
+            LAUNCH_TIMED(e, today, REINA_PK_DAY, (k_day<M::group, M::exact, M::sparse>), grid, dim3(DAY_THREADS), lds, s, refs, e->h_ref, dp, p.lds_rows,
+                         p.lds_crows, e->day_flags, p.stream_imports);
+    });
+    if (p.presort_grid)   // a sharded population: its event buckets sorted and their maps written to the exchange block BEFORE the all-reduce
+        LAUNCH_DAY(e, today, REINA_PK_HOSP_SORT, k_hosp_presort, dim3(p.presort_grid, K), dim3(HOSP_THREADS), (size_t)HOSP_P_THREADS * HOSP_P_E * 8, s, dp);
 }
-
-static int launch_day_begin(reina_engine_t *e, const MemberRef *refs, uint32_t K, const reina_day_t &dp,
-                            uint32_t hist_slot, hipStream_t s) {
-    if (int rc = launch_day_open(e, refs, K, dp, hist_slot, s)) return rc;
-    if (int rc = launch_day_trace(e, refs, K, dp, s)) return rc;
-    return launch_day_main(e, refs, K, dp, s);
-}
-
 // REINA_PH_FEEDBACK (exact attribution): the sources of the day's cross-shard infections take their infectees
-static int launch_day_feedback(reina_engine_t *e, const MemberRef *refs, uint32_t K, const reina_day_t &dp, hipStream_t s) {
-    if (!e->exact) return REINA_OK;
+static void launch_day_feedback(reina_engine_t *e, const MemberRef *refs, uint32_t K, const reina_day_t &dp, const DayPlan &p, hipStream_t s) {
+    if (!e->exact) return;
     const int today = profiled_kind(e, dp.day);
-    LAUNCH_DAY(e, today, REINA_PK_XCHG, k_feedback, dim3(xchg_grid(e), K), dim3(256), 0, s, dp);
-    HIP_CHECK(hipGetLastError());
-    return REINA_OK;
+    LAUNCH_DAY(e, today, REINA_PK_XCHG, k_feedback, dim3(p.xchg_grid, K), dim3(256), 0, s, dp);
 }
-
-static int launch_day_end(reina_engine_t *e, const MemberRef *refs, uint32_t K, const reina_day_t &dp, hipStream_t s) {
-    const uint32_t N = e->cfg.n_agents;
+// REINA_PH_END: (k_remote, which also takes this shard's share of the pooled free beds / ICU units: the walk starts from it,) the installs
+static void launch_day_end(reina_engine_t *e, const MemberRef *refs, uint32_t K, const reina_day_t &dp, const DayPlan &p, hipStream_t s) {
     const int today = profiled_kind(e, dp.day);
-    const bool sharded = e->cfg.n_shards > 1;
-    if (sharded)   // (also takes this shard's share of the pooled free beds / ICU units: the walk below starts from it)
-        LAUNCH_DAY(e, today, REINA_PK_REMOTE, k_remote, dim3(grid_for(N / 256 + 1, 256, 256), K), dim3(256), 0, s, dp);
-    {
-        const uint32_t scan_tiles = ((N >> 2) + 127u) / 128u;
-        const uint32_t scan_waves = e->cur_scan_waves;
-        // installing workgroups: one wave per unit of a quiet day (3 lists of scan_waves / 8 units + the event buckets), so
-        // that no wave walks two dependent chains one after the other; at most one workgroup per CU
-        int ig = grid_for(N / 64 + 1, HOSP_THREADS, 128) * 2;
-        {
-            const uint32_t units = 3u * ((scan_waves + 7u) / 8u) + (e->h_params.hosp_ranges + 7u) / 8u;
-            const int want = (int)((units + HOSP_THREADS / 64 - 1) / (HOSP_THREADS / 64));
-            if (want > ig) ig = want;
-            if (ig > (int)e->n_cus) ig = (int)e->n_cus;
-        }
-        // (groups: 128 workgroups for all members together -- every workgroup pays its prologue and its histogram flush)
-        // (a group of 128 HUS members, measured in round 4: ONE installing workgroup per member beside the one for the events --
-        // 256 workgroups, one per CU, all resident together -- 67 us a launch against 72.5 with two, 70 with three)
-        if (K > 1 && ig > (int)(128 / K)) ig = (int)(128 / K) >= 2 ? ((int)(128 / K) & ~1) : 1;
-        const bool par = e->h_params.hosp_parallel != 0;
-        if (par) {
-            // a large population: the launch's first workgroups are the walkers of a day on which the events' order matters
-            // (one wave per priority bucket: R / 16 workgroups; on any other day they install too), the others install.
-            // One workgroup of 1024 threads per CU: all of them resident together, so the walk runs beside the installs.
-            const uint32_t n_walk = (e->h_params.hosp_ranges + e->walk_div - 1u) / e->walk_div;
-            int rest = (int)e->n_cus - (int)n_walk;
-            if (K > 1) rest = (int)(e->n_cus / K) - (int)n_walk;
-            if (rest > ig) rest = ig;
-            if (rest < 2) rest = 2;
-            LAUNCH_DAY(e, today, REINA_PK_INSTALL, k_hosp_install, dim3(n_walk + rest, K), dim3(HOSP_THREADS),
-                         (size_t)HOSP_P_THREADS * HOSP_P_E * 8, s, dp, scan_waves, scan_tiles, HI_INSTALL | HI_EVENTS, n_walk);
-        } else {
-            // workgroup 0 walks the bed / ICU events of a day on which order matters, beside the installs
-            if (ig < 2 && K == 1) ig = 2;
-            LAUNCH_DAY(e, today, REINA_PK_INSTALL, k_hosp_install, dim3(ig + 1, K), dim3(HOSP_THREADS), (size_t)REINA_MAX_HOSP_EVENTS * 8, s, dp, scan_waves, scan_tiles, HI_HOSP_WG | HI_INSTALL | HI_EVENTS, 0u);
-        }
-    }
-    HIP_CHECK(hipGetLastError());
-    return REINA_OK;
+    if (p.remote_grid) LAUNCH_DAY(e, today, REINA_PK_REMOTE, k_remote, dim3(p.remote_grid, K), dim3(256), 0, s, dp);
+    const size_t lds = p.install_walk_lds ? (size_t)HOSP_P_THREADS * HOSP_P_E * 8 : (size_t)REINA_MAX_HOSP_EVENTS * 8;
+    LAUNCH_DAY(e, today, REINA_PK_INSTALL, k_hosp_install, dim3(p.install_grid, K), dim3(HOSP_THREADS), lds, s, dp, p.scan_waves, p.scan_tiles,
+               (int)p.install_flags, p.n_walk);
 }
 
 // A stretch of days of a small unsharded population as ONE launch (k_small.inc).  Every workgroup of it must be resident at once
@@ -920,20 +727,17 @@ static bool small_days_engine_ok(const reina_engine_t *e) {
     if ((uint32_t)g_live_engines.load() * e->small_wgs > e->n_cus) return false;
     return SMALL_TAIL_BYTES + e->small_static_lds <= 160u * 1024u;
 }
-// the record of one day, or false: the day takes the three launches
+// the record of one day from its plan, or false: the day takes the three launches
 static bool small_day_record(reina_engine_t *e, const reina_day_t &dp, SmallDayRec *rec) {
     if (dp.n_vaccinations != 0u) return false;
-    DayGeom geo;
-    if (day_geometry(e, 1, dp, &geo) != REINA_OK) return false;
-    const uint32_t W = e->small_wgs;
-    const uint32_t helpers = geo.weekly_own == OPEN_WEEKLY_IN_STREAM ? 0u : geo.weekly_own > 0 ? (uint32_t)geo.weekly_own : (uint32_t)-geo.weekly_own;
-    if (W < 1u + (helpers > 1u ? helpers : 1u) + 1u || geo.stream_imports > 1u) return false;
+    DayPlan p;
+    note_testing(e, dp);
+    if (plan_engine_day(e, 1, dp, &p) != REINA_OK || !plan_fits_small(launch_shape(e), p)) return false;
     std::memset(rec, 0, sizeof(*rec));
     rec->dp = dp;
-    rec->weekly_own = geo.weekly_own;
-    const bool ct = dp.testing_mode == RT_ALL_WITH_SYMPTOMS_CT;
-    rec->mode = !e->testing_ever ? 0 : ct ? 3 : 1;   // (launch_day_open: a population this small walks level 1 in the opening)
-    rec->stream_imports = geo.stream_imports;
+    rec->weekly_own = p.weekly_own;
+    rec->mode = (int32_t)p.open_mode;
+    rec->stream_imports = p.stream_imports;
     return true;
 }
 static int launch_small_days(reina_engine_t *e, const SmallDayRec *recs, uint32_t n, hipStream_t s) {
@@ -947,31 +751,24 @@ static int launch_small_days(reina_engine_t *e, const SmallDayRec *recs, uint32_
     hipLaunchKernelGGL(k_upload, dim3(words / 256u + 1u < 64u ? words / 256u + 1u : 64u), dim3(256), 0, s, reinterpret_cast<uint32_t *>(e->d_days),
                        reinterpret_cast<const uint32_t *>(dsrc), words, (uint32_t *)nullptr, (const uint32_t *)nullptr, none);
     if (int rc = e->days_stage.release_behind(s)) return rc;
-    const uint32_t N = e->cfg.n_agents, W = e->small_wgs;
+    const uint32_t W = e->small_wgs;
+    const LaunchShape sh = launch_shape(e);
     SmallGeom g;
     std::memset(&g, 0, sizeof(g));
     g.n_days = n;
-    g.lds_rows = e->h_tables.n_rows > REINA_LDS_ROWS ? REINA_LDS_ROWS : e->h_tables.n_rows;
-    g.lds_crows = e->h_tables.n_crows > REINA_LDS_CROWS ? REINA_LDS_CROWS : e->h_tables.n_crows;
-    if (e->lds_rows_cap && g.lds_rows > e->lds_rows_cap) g.lds_rows = e->lds_rows_cap;
-    if (e->lds_rows_cap && g.lds_crows > e->lds_rows_cap) g.lds_crows = e->lds_rows_cap;
+    g.lds_rows = lds_rows_for(sh, e->h_tables.n_rows, REINA_LDS_ROWS);
+    g.lds_crows = lds_rows_for(sh, e->h_tables.n_crows, REINA_LDS_CROWS);
     g.day_flags = e->day_flags;
-    g.scan_tiles = ((N >> 2) + 127u) / 128u;
+    g.scan_tiles = scan_tiles_for(sh.n_agents);
     g.bar_base = e->bar_epoch;
     g.bar = e->d_bar;
     g.days = e->d_days;
     e->bar_epoch += SMALL_BARRIERS_PER_DAY * n;
-    e->cur_scan_waves = (W - 1u) * DAY_WAVES;
     // (timed as a whole on the stretches that begin on one of the two profiled phases; the kind's "launches" count DAYS: its mean is per day)
     const int today = profiled_kind(e, recs[0].dp.day);
-    size_t ev_a, ev_b;
-    if (kind_timed(today, REINA_PK_SMALL_DAY) && take_event_pair(e, &ev_a, &ev_b)) {
-        hipExtLaunchKernelGGL(k_small_days, dim3(W), dim3(HOSP_THREADS), SMALL_TAIL_BYTES, s, e->ev_pool[ev_a], e->ev_pool[ev_b], 0, e->h_ref, g);
-        e->kpairs[REINA_PK_SMALL_DAY].emplace_back(ev_a, ev_b);
-        e->small_pair_days.push_back(n);
-    } else {
-        hipLaunchKernelGGL(k_small_days, dim3(W), dim3(HOSP_THREADS), SMALL_TAIL_BYTES, s, e->h_ref, g);
-    }
+    const size_t timed_before = e->kpairs[REINA_PK_SMALL_DAY].size();
+    LAUNCH_TIMED(e, today, REINA_PK_SMALL_DAY, k_small_days, dim3(W), dim3(HOSP_THREADS), SMALL_TAIL_BYTES, s, e->h_ref, g);
+    if (e->kpairs[REINA_PK_SMALL_DAY].size() > timed_before) e->small_pair_days.push_back(n);
     HIP_CHECK(hipGetLastError());
     return REINA_OK;
 }
@@ -979,15 +776,18 @@ static int launch_small_days(reina_engine_t *e, const SmallDayRec *recs, uint32_
 static int run_days_small(reina_engine_t *e, const reina_day_t *days, uint32_t n_days, int32_t *history_base, hipStream_t s) {
     std::vector<SmallDayRec> recs;
     recs.reserve(SMALL_MAX_DAYS);
+    auto day_at = [&](uint32_t k) {
+        reina_day_t d = days[k];
+        if (history_base) d.history_row = history_base + (size_t)k * REINA_COUNTER_WORDS;
+        return d;
+    };
     uint32_t k = 0;
     while (k < n_days) {
         recs.clear();
         uint32_t m = 0;
         while (k + m < n_days && m < SMALL_MAX_DAYS) {
-            reina_day_t d = days[k + m];
-            if (history_base) d.history_row = history_base + (size_t)(k + m) * REINA_COUNTER_WORDS;
             SmallDayRec r;
-            if (!small_day_record(e, d, &r)) break;
+            if (!small_day_record(e, day_at(k + m), &r)) break;
             recs.push_back(r);
             m++;
         }
@@ -999,61 +799,67 @@ static int run_days_small(reina_engine_t *e, const reina_day_t *days, uint32_t n
         // (one qualifying day between two that do not, or none: the launches)
         const uint32_t take = m ? m : 1u;
         for (uint32_t q = 0; q < take; q++) {
-            reina_day_t d = days[k + q];
-            if (history_base) d.history_row = history_base + (size_t)(k + q) * REINA_COUNTER_WORDS;
-            for (int ph = 0; ph < REINA_PH_NR; ph++) {
-                const int need = reina_step_phase(e, &d, ph, s);
-                if (need < 0) return need;
-            }
+            const reina_day_t d = day_at(k + q);
+            if (int rc = reina_step_day(e, &d, s)) return rc;
         }
         k += take;
     }
     return REINA_OK;
 }
 
-int reina_step_phase(reina_engine_t *e, const reina_day_t *day, int phase, void *stream) {
-    if (!e || !day) return REINA_E_INVALID;
-    if (!e->bound) return REINA_E_NOT_BOUND;
-    hipStream_t s = (hipStream_t)stream;
-    const bool xtrace = e->exact && day->testing_mode == RT_ALL_WITH_SYMPTOMS_CT;
-    int rc;
+// one phase of a planned day; > 0: the collectives that must follow it
+static int step_phase_planned(reina_engine_t *e, const reina_day_t &day, const DayPlan &p, int phase, hipStream_t s) {
+    int need = 0;
     switch (phase) {
-    case REINA_PH_OPEN:
-        rc = launch_day_open(e, e->d_ref, 1, *day, 0, s);
-        return rc ? rc : (xtrace ? REINA_X_ALLTOALL : 0);
-    case REINA_PH_TRACE:
-        rc = launch_day_trace(e, e->d_ref, 1, *day, s);
-        return rc ? rc : (xtrace ? REINA_X_ALLTOALL : 0);
+    case REINA_PH_OPEN: launch_day_open(e, e->d_ref, 1, day, p, 0, s), need = p.xtrace ? REINA_X_ALLTOALL : 0; break;
+    case REINA_PH_TRACE: launch_day_trace(e, e->d_ref, 1, day, p, s), need = p.xtrace ? REINA_X_ALLTOALL : 0; break;
     case REINA_PH_MAIN:
-        rc = launch_day_main(e, e->d_ref, 1, *day, s);
         // (a single shard with a collective set exchanges too: the one-GPU box exercises the call)
         // exact attribution (round 6, ABI 7): what the all-reduce carries -- the shards' capacity words and event maps -- rides in the
         // trailers of the contact records' segments: ONE collective here, not two
-        if (rc) return rc;
-        if (e->exact) return REINA_X_ALLTOALL;
-        return (e->cfg.n_shards > 1 || e->coll_fn) ? REINA_X_ALLREDUCE : 0;
-    case REINA_PH_END:
-        rc = launch_day_end(e, e->d_ref, 1, *day, s);
-        return rc ? rc : (e->exact ? REINA_X_ALLTOALL : 0);
-    case REINA_PH_FEEDBACK:
-        return launch_day_feedback(e, e->d_ref, 1, *day, s);
+        launch_day_main(e, e->d_ref, 1, day, p, s);
+        need = e->exact ? REINA_X_ALLTOALL : (e->cfg.n_shards > 1 || e->coll_fn) ? REINA_X_ALLREDUCE : 0;
+        break;
+    case REINA_PH_END: launch_day_end(e, e->d_ref, 1, day, p, s), need = e->exact ? REINA_X_ALLTOALL : 0; break;
+    default: launch_day_feedback(e, e->d_ref, 1, day, p, s);
     }
-    return refuse("phase out of range");
+    HIP_CHECK(hipGetLastError());
+    return need;
+}
+// what every stateless entry point of a single engine begins with: the arguments, then the day's plan
+static int begin_step(reina_engine_t *e, const reina_day_t *day, DayPlan *p) {
+    if (!e || !day) return REINA_E_INVALID;
+    if (!e->bound) return REINA_E_NOT_BOUND;
+    note_testing(e, *day);
+    return plan_engine_day(e, 1, *day, p);
+}
+
+int reina_step_phase(reina_engine_t *e, const reina_day_t *day, int phase, void *stream) {
+    DayPlan p;
+    if (e && day && e->bound && (phase < 0 || phase >= REINA_PH_NR)) return refuse("phase out of range");
+    if (int rc = begin_step(e, day, &p)) return rc;
+    return step_phase_planned(e, *day, p, phase, (hipStream_t)stream);
 }
 
 // the two halves of a day around its one all-reduce (a population without exact attribution)
+static const char *const EXACT_HALVES = "exact attribution: a day has more than one exchange -- step it by reina_step_phase (or reina_step_day with reina_set_alltoall)";
 int reina_step_day_begin(reina_engine_t *e, const reina_day_t *day, void *stream) {
-    if (!e || !day) return REINA_E_INVALID;
-    if (!e->bound) return REINA_E_NOT_BOUND;
-    if (e->exact) return refuse("exact attribution: a day has more than one exchange -- step it by reina_step_phase (or reina_step_day with reina_set_alltoall)");
-    return launch_day_begin(e, e->d_ref, 1, *day, 0, (hipStream_t)stream);
+    DayPlan p;
+    if (e && day && e->bound && e->exact) return refuse(EXACT_HALVES);
+    if (int rc = begin_step(e, day, &p)) return rc;
+    for (int ph = REINA_PH_OPEN; ph <= REINA_PH_MAIN; ph++) {
+        const int need = step_phase_planned(e, *day, p, ph, (hipStream_t)stream);
+        if (need < 0) return need;
+    }
+    return REINA_OK;
 }
 
 int reina_step_day_end(reina_engine_t *e, const reina_day_t *day, void *stream) {
-    if (!e || !day) return REINA_E_INVALID;
-    if (!e->bound) return REINA_E_NOT_BOUND;
-    if (e->exact) return refuse("exact attribution: a day has more than one exchange -- step it by reina_step_phase (or reina_step_day with reina_set_alltoall)");
-    return launch_day_end(e, e->d_ref, 1, *day, (hipStream_t)stream);
+    DayPlan p;
+    if (e && day && e->bound && e->exact) return refuse(EXACT_HALVES);
+    if (int rc = begin_step(e, day, &p)) return rc;
+    const int need = step_phase_planned(e, *day, p, REINA_PH_END, (hipStream_t)stream);
+    return need < 0 ? need : REINA_OK;
 }
 
 int reina_set_collective(reina_engine_t *e, reina_allreduce_fn allreduce, void *comm) {
@@ -1071,8 +877,10 @@ int reina_set_alltoall(reina_engine_t *e, reina_alltoall_fn alltoall, void *comm
 }
 
 int reina_step_day(reina_engine_t *e, const reina_day_t *day, void *stream) {
+    DayPlan p;
+    if (int rc = begin_step(e, day, &p)) return rc;
     for (int ph = 0; ph < REINA_PH_NR; ph++) {
-        const int need = reina_step_phase(e, day, ph, stream);
+        const int need = step_phase_planned(e, *day, p, ph, (hipStream_t)stream);
         if (need < 0) return need;
         // the exchanges of a sharded population, queued on the day stream itself (on the profiled days of the event-walk kind an
         // event pair is recorded around them: `collective` of reina_profile_read_kernels -- what RCCL costs a day, apart from the kernels)
@@ -1094,24 +902,22 @@ int reina_step_day(reina_engine_t *e, const reina_day_t *day, void *stream) {
     return REINA_OK;
 }
 
-int reina_run_days(reina_engine_t *e, const reina_day_t *days, uint32_t n_days, void *stream) {
-    if (e && days && e->bound && n_days >= 2u && small_days_engine_ok(e)) return run_days_small(e, days, n_days, nullptr, (hipStream_t)stream);
+// `rows`: the history rows laid out from history_base (none if null); otherwise every day keeps its own history_row
+static int run_days(reina_engine_t *e, const reina_day_t *days, uint32_t n_days, bool rows, int32_t *history_base, void *stream) {
+    if (e && days && e->bound && n_days >= 2u && small_days_engine_ok(e)) return run_days_small(e, days, n_days, history_base, (hipStream_t)stream);
     for (uint32_t k = 0; k < n_days; k++) {
-        int rc = reina_step_day(e, &days[k], stream);
-        if (rc) return rc;
+        reina_day_t d;
+        if (rows) {
+            d = days[k];
+            d.history_row = history_base ? history_base + (size_t)k * REINA_COUNTER_WORDS : nullptr;
+        }
+        if (int rc = reina_step_day(e, rows ? &d : &days[k], stream)) return rc;
     }
     return REINA_OK;
 }
-
+int reina_run_days(reina_engine_t *e, const reina_day_t *days, uint32_t n_days, void *stream) { return run_days(e, days, n_days, false, nullptr, stream); }
 int reina_run_days_hist(reina_engine_t *e, const reina_day_t *days, uint32_t n_days, int32_t *history_base, void *stream) {
-    if (e && days && e->bound && n_days >= 2u && small_days_engine_ok(e)) return run_days_small(e, days, n_days, history_base, (hipStream_t)stream);
-    for (uint32_t k = 0; k < n_days; k++) {
-        reina_day_t d = days[k];
-        d.history_row = history_base ? history_base + (size_t)k * REINA_COUNTER_WORDS : nullptr;
-        int rc = reina_step_day(e, &d, stream);
-        if (rc) return rc;
-    }
-    return REINA_OK;
+    return run_days(e, days, n_days, true, history_base, stream);
 }
 
 struct reina_group {
@@ -1229,9 +1035,16 @@ static int group_run_days(reina_group_t *g, const reina_day_t *days, uint32_t n_
     for (uint32_t d = 0; d < n_days; d++) {
         reina_day_t dp = days[d];
         dp.history_row = nullptr;
+        DayPlan p;
         int rc = hooks.before ? hooks.before(hooks.a, dp, s) : REINA_OK;
-        if (rc == REINA_OK) rc = launch_day_begin(e0, g->d_refs, K, dp, d, s);
-        if (rc == REINA_OK) rc = launch_day_end(e0, g->d_refs, K, dp, s);
+        if (rc == REINA_OK) note_testing(e0, dp), rc = plan_engine_day(e0, K, dp, &p);
+        if (rc == REINA_OK) {
+            launch_day_open(e0, g->d_refs, K, dp, p, d, s);
+            launch_day_trace(e0, g->d_refs, K, dp, p, s);
+            launch_day_main(e0, g->d_refs, K, dp, p, s);
+            launch_day_end(e0, g->d_refs, K, dp, p, s);
+            HIP_CHECK_OR(hipGetLastError(), e0->h_ref = own_ref);
+        }
         if (rc == REINA_OK && hooks.after) rc = hooks.after(hooks.a, dp, s);
         if (rc) {
             e0->h_ref = own_ref;
@@ -1239,10 +1052,7 @@ static int group_run_days(reina_group_t *g, const reina_day_t *days, uint32_t n_
         }
     }
     e0->h_ref = own_ref;
-    for (auto m : g->members) {
-        m->testing_ever = m->testing_ever || e0->testing_ever;
-        m->cur_scan_waves = e0->cur_scan_waves;
-    }
+    for (auto m : g->members) m->testing_ever = m->testing_ever || e0->testing_ever;
     return REINA_OK;
 }
 
