@@ -45,6 +45,19 @@ def build(force=False, verbose=False):
     return LIB
 
 
+def build_variant(defines, out_path, verbose=False):
+    """A diagnostic or code variant of the library: build()'s flags plus one -D per entry of `defines` ('REINA_OPEN_STAMPS',
+    'REINA_DAY_PROF=9', ...), written to the side file `out_path` (selected at run time by REINA_HIP_LIB)."""
+    out_path = os.path.abspath(out_path)
+    if out_path == os.path.abspath(LIB):
+        raise ValueError('a variant is a side file: %s is the production library' % LIB)
+    cmd = [hipcc_path()] + HIPCC_FLAGS + ['-D' + d for d in defines] + ['-o', out_path] + SOURCES
+    if verbose:
+        print(' '.join(cmd))
+    subprocess.run(cmd, check=True)
+    return out_path
+
+
 if __name__ == '__main__':
     build(force='--force' in sys.argv, verbose=True)
     print(LIB)

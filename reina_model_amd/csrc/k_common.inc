@@ -66,6 +66,7 @@ struct Tables {  // bigger tables staged into LDS by k_day
     uint32_t age_shift;
     uint8_t age_block[REINA_AGE_BLOCKS];
 };
+#include "reina_diag.h"     // the diagnostic builds: slot map of buffers.mirror, the stamp, PROF_* / ABLATED
 #include "reina_launch.h"   // REINA_LDS_ROWS / _CROWS, the block shapes and thresholds of the day's kernels, VaccGeom, the HI_* flags
 
 // Pointers that reach a kernel through MemberRef (an array in HBM) are generic to the compiler, and

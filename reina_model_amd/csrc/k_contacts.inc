@@ -18,19 +18,9 @@
 //
 // Everything a contact decides is keyed by (source, day, contact number), so results do not depend on which
 // wave samples it, in which batch or in which order: bit-identical to oracle B's sequential loops.
-// k_day's launch flags (diagnostics and measurements; 0 in production)
-// -DREINA_DAY_PROF (tools/day_prof.py): every wave sums the shader-clock cycles it spends in the parts of its loop; lane 0
-// adds them to buffers.mirror[32 + k] when the wave is through (k: 0 whole loop, 1 feed, 2 wait for fetched words, 3 wait for a
-// chunk of bits, 4 state-machine rounds, 5 contact batches, 6 of which resolve turns, 7 tail resolve; [48 + k]: counts)
-#ifdef REINA_DAY_PROF   // = the ONE part timed beside the whole loop (two 32-bit sums: anything more perturbs the kernel)
-#define PROF_DECL uint32_t prof_t_ = 0, prof_n_ = 0, prof_s_ = 0, prof_all_ = 0
-#define PROF_BEGIN(k) do { if ((k) == REINA_DAY_PROF || (k) == 0) { const uint32_t t_ = (uint32_t)__builtin_amdgcn_s_memtime(); if ((k) == 0) prof_all_ = t_; else prof_s_ = t_; } } while (0)
-#define PROF_END(k) do { if ((k) == REINA_DAY_PROF) { prof_t_ += (uint32_t)__builtin_amdgcn_s_memtime() - prof_s_; prof_n_++; } else if ((k) == 0) prof_all_ = (uint32_t)__builtin_amdgcn_s_memtime() - prof_all_; } while (0)
-#else
-#define PROF_DECL
-#define PROF_BEGIN(k) do { } while (0)
-#define PROF_END(k) do { } while (0)
-#endif
+// Diagnostic builds (reina_diag.h; tools/diag.py builds and reads them): -DREINA_DAY_PROF=<part> -- every wave sums the shader-clock
+// cycles of its whole loop and of ONE named part of it (PROF_BEGIN / PROF_END / PROF_IS; the names: DIAG_PROF_PARTS) and lane 0 writes them as the
+// wave's row of the map's WAVES region when the wave is through --, -DREINA_DAY_STAMPS, -DREINA_ABLATE (ABLATED).
 #define NEEDY_ENTRIES 128                     // queued (agent, word) pairs: fewer than 64 carried over + at most 64 per feeding step
 #define DAY_XSTAGE (REINA_PRESSURE_WORDS / 2 - 1)   // exact attribution: contact records a workgroup stages in LDS (the pressure block's 8 KB: a count + 1023 records)
 
@@ -126,9 +116,7 @@ struct ContactState {
     // ... and the parameters the batches and the resolve steps ask at every turn, pinned the same way (each was a scalar load and a
     // wait of its own where it was used: five in a row per resolve turn)
     uint32_t n_shards, shard_rank, age_shift, nr_ages;
-#ifdef REINA_DAY_PROF
-    uint32_t prof_in, prof_in_n;
-#endif
+    PROF_IN_MEMBERS;   // (REINA_DAY_PROF: the sums of a part that lies inside contact_batch)
 };
 
 // The contacts that CAN transmit -- contacts whose transmission draw lies below the source's largest possible transmission
@@ -235,7 +223,7 @@ __device__ __forceinline__ void resolve_finish(PT P, const CAS Tables *T, const 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     bool hit = false;
     uint4 cand = make_uint4(0xFFFFFFFFu, 0, 0, 0);
-    if (ABLATED(1u)) return;
+    if (ABLATED(RESOLVE)) return;
     if ((uint32_t)lane < n) {
         const uint32_t src = S.pend_src[wave][first + lane], pe = S.pend_info[wave][first + lane];
         const uint32_t c = pe & 0xFFu, l2 = (pe >> 8) & 0xFFu;
@@ -389,16 +377,13 @@ __device__ __forceinline__ void contact_batch(PT P, const CAS Tables *T, const G
     const CAS reina_disease_t &d = P->dis;
     uint4 it = make_uint4(0, 0, 0, 0);
     uint32_t nr = 0;
-#if defined(REINA_DAY_PROF) && (REINA_DAY_PROF == 8 || REINA_DAY_PROF == 9)
-    uint32_t pb_ = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
-#if defined(REINA_DAY_PROF) && (REINA_DAY_PROF == 10 || REINA_DAY_PROF == 11)
-    // 10: how long the wave's memory operations in flight take to drain at the head of a batch; 11: the head behind that drain
-    uint32_t pb_ = (uint32_t)__builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (REINA_DAY_PROF == 10) { C.prof_in += (uint32_t)__builtin_amdgcn_s_memtime() - pb_; C.prof_in_n++; }
-    pb_ = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
+    PROF_IN_VAR(pb_);
+    if (PROF_IS(BATCH_HEAD) || PROF_IS(BATCH_STEPS) || PROF_IS(HEAD_DRAIN) || PROF_IS(HEAD_DRAINED)) PROF_IN_MARK(pb_);
+    if (PROF_IS(HEAD_DRAIN) || PROF_IS(HEAD_DRAINED)) {   // the wave's memory operations in flight drained at the head of a batch: the drain, or the head behind it
+        PROF_DRAIN();
+        if (PROF_IS(HEAD_DRAIN)) PROF_IN_ADD(C, pb_, 1u);
+        PROF_IN_MARK(pb_);
+    }
     if ((uint32_t)lane < n) {
         const uint2 ex = rec[lane];
         const uint32_t i = ex.x, w = ex.y;
@@ -415,7 +400,7 @@ __device__ __forceinline__ void contact_batch(PT P, const CAS Tables *T, const G
         const uint32_t crow = S.crow_of_age[age];
         const bool in_lds = crow < lds_crows;
         int nn;
-        if (ABLATED(2u)) {
+        if (ABLATED(COUNT_DRAW)) {
             nn = (int)((i * 2654435761u) >> 30) + 1;
         } else if (st == RS_ILLNESS && sev != RV_ASYMPTOMATIC) {
             // (LDS rows and rows read through L2 apart: chosen per threshold, every one of the five LDS reads stood behind a wait
@@ -469,13 +454,8 @@ __device__ __forceinline__ void contact_batch(PT P, const CAS Tables *T, const G
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): wave-private LDS rows written
     __builtin_amdgcn_wave_barrier();
     C.wave_contacts += total;
-#if defined(REINA_DAY_PROF) && (REINA_DAY_PROF == 8 || REINA_DAY_PROF == 11)
-    C.prof_in += (uint32_t)__builtin_amdgcn_s_memtime() - pb_;
-    C.prof_in_n++;
-#endif
-#if defined(REINA_DAY_PROF) && REINA_DAY_PROF == 9
-    pb_ = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
+    if (PROF_IS(BATCH_HEAD) || PROF_IS(HEAD_DRAINED)) PROF_IN_ADD(C, pb_, 1u);
+    if (PROF_IS(BATCH_STEPS)) PROF_IN_MARK(pb_);
     // The owning source of contact j is the number of sources that lie wholly before it, E(j) = #{s : inc[s] <= j}.  Per step
     // of 64 contacts: every source whose contacts END inside the step's window marks the position (LDS counters, one add per
     // such source), a prefix sum over the window (six cross-lane moves) + the sources that ended before it = E.  (Rounds
@@ -489,7 +469,7 @@ __device__ __forceinline__ void contact_batch(PT P, const CAS Tables *T, const G
 #ifndef REINA_NO_DAY_PRIO
     __builtin_amdgcn_s_setprio(0);
 #endif
-    for (uint32_t j0 = 0; j0 < (ABLATED(4u) ? 0u : total); j0 += 64) {
+    for (uint32_t j0 = 0; j0 < (ABLATED(CONTACTS) ? 0u : total); j0 += 64) {
         S_cnt[lane] = 0u;
         __builtin_amdgcn_wave_barrier();
         if (inc - j0 < 64u) atomicAdd(&S_cnt[inc - j0], 1u);
@@ -551,9 +531,8 @@ __device__ __forceinline__ void contact_batch(PT P, const CAS Tables *T, const G
             }
             if (cnt >= room) {
                 C.n_pend = 64u;
-#if defined(REINA_DAY_PROF) && REINA_DAY_PROF == 6
-                const uint32_t pt_ = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
+                PROF_IN_VAR(pt_);
+                if (PROF_IS(RESOLVE_TURNS)) PROF_IN_MARK(pt_);
 #ifndef REINA_NO_DAY_PRIO
                 __builtin_amdgcn_s_setprio(3);   // (the turn ends with the targets' gather going out: the sooner the better)
 #endif
@@ -561,10 +540,7 @@ __device__ __forceinline__ void contact_batch(PT P, const CAS Tables *T, const G
 #ifndef REINA_NO_DAY_PRIO
                 __builtin_amdgcn_s_setprio(0);
 #endif
-#if defined(REINA_DAY_PROF) && REINA_DAY_PROF == 6
-                C.prof_in += (uint32_t)__builtin_amdgcn_s_memtime() - pt_;
-                C.prof_in_n++;
-#endif
+                if (PROF_IS(RESOLVE_TURNS)) PROF_IN_ADD(C, pt_, 1u);
                 if (poss && rank >= room) {
                     const uint32_t q = C.cur * 64u + rank - room;
                     S.pend_src[wave][q] = pe_src;
@@ -577,10 +553,7 @@ __device__ __forceinline__ void contact_batch(PT P, const CAS Tables *T, const G
             }
         }
     }
-#if defined(REINA_DAY_PROF) && REINA_DAY_PROF == 9
-    C.prof_in += (uint32_t)__builtin_amdgcn_s_memtime() - pb_;
-    C.prof_in_n += (total + 63u) / 64u;
-#endif
+    if (PROF_IS(BATCH_STEPS)) PROF_IN_ADD(C, pb_, (total + 63u) / 64u);
     __builtin_amdgcn_wave_barrier();
 }
 
@@ -606,9 +579,7 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
     const ParamsX<EXACT> P{(const CAS DevParams *)mref_.P};
     const GBuffers B = global_buffers(mref_.B);  // by value: pointers live in SGPRs, never re-read after stores
     const CAS Tables *T = (const CAS Tables *)mref_.T;
-#ifdef REINA_DAY_STAMPS
-    const uint64_t ds_t0 = wall_clock64();
-#endif
+    DIAG_CLOCK(DAY, ds_t0);   // (-DREINA_DAY_STAMPS: where an (almost) empty day's k_day spends its time, thread 0 of every workgroup)
     // the LDS image is carved for lds_rows_launch rows (the same for every member of a group); this member fills
     // and uses min(its own distinct rows, that)
     const uint32_t lds_rows = T->n_rows < lds_rows_launch ? T->n_rows : lds_rows_launch;
@@ -829,12 +800,7 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
             for (int k = tid; k < REINA_PRESSURE_WORDS; k += DAY_THREADS) S_pressure[k] = 0;
     }
     __syncthreads();
-#ifdef REINA_DAY_STAMPS   // diagnostic builds (tools/day_stamps.py): where an (almost) empty day's k_day spends its time
-#define DSTAMP(k) do { if (tid == 0) atomicAdd((unsigned long long *)&B.mirror[56 + (k)], (unsigned long long)(wall_clock64() - ds_t0)); } while (0)
-    DSTAMP(0);
-#else
-#define DSTAMP(k) do { } while (0)
-#endif
+    DIAG_SINCE(DAY, DIAG_DAY_STAGED, DIAG_THREAD0, ds_t0, B.mirror);
     ScanLists L;
     ContactState C;
     {
@@ -860,9 +826,7 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
         C.shard_rank = opaque_s(P->shard_rank);
         C.age_shift = opaque_s(T->age_shift);
         C.nr_ages = opaque_s((uint32_t)P->nr_ages);
-#ifdef REINA_DAY_PROF
-        C.prof_in = C.prof_in_n = 0;
-#endif
+        PROF_IN_RESET(C);
     }
     // The wave's LDS queues: nq = (agent, hot word) pairs awaiting the state machine, filled from the tiles (dense day:
     // the words are in the tile's registers) or from the fetches (sparse day); xq (L.strip) = infectious agents found by
@@ -897,7 +861,7 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
         DAY_PUSH(in && (w & RH_ACTIVE), i, w);
     }
     PROF_DECL;
-    PROF_BEGIN(0);
+    PROF_BEGIN(LOOP);
     // Wave priorities by PHASE (round 5): the feed and the state-machine rounds are chains of dependent steps with few vector
     // instructions between them, a contact batch is vector instructions back to back.  The SIMD issues its oldest wave first;
     // with the chains above the batches, a wave in its feed gets its few instructions out between the multiplies of the others'
@@ -907,7 +871,7 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
 #ifndef REINA_NO_DAY_PRIO
         __builtin_amdgcn_s_setprio(3);
 #endif
-        PROF_BEGIN(1);
+        PROF_BEGIN(FEED);
         if (plain) {
             // The fused day of a small population (k_small_day): a wave's tiles are a handful, the launch has a few dozen
             // workgroups -- the bits of sixteen tiles by one ordinary 16-byte load per lane, the set bits to agent numbers exactly as
@@ -958,12 +922,12 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
             //   (2) bits -> agent numbers (iq): every lane that has a bit left queues the agent of its lowest one, at most 64
             //       a step; a chunk that is used up is replaced from its register set, which is requested again five ahead;
             //   (3) the next (up to) 64 agents of iq: their hot words requested into v124.
-            PROF_BEGIN(14);
+            PROF_BEGIN(SPARSE_WORDS);
             if (fl_n && nqn < 64u) {
                 uint32_t w;
-                PROF_BEGIN(2);
+                PROF_BEGIN(FETCH_WAIT);
                 asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, v124" : "=v"(w) : : "memory");
-                PROF_END(2);
+                PROF_END(FETCH_WAIT);
                 // (the word's own ACTIVE flag is asked again: the bit plane is a caller-visible buffer, and a word that does not agree
                 // with its bit must not reach the state machine -- round-4 advisor)
                 DAY_PUSH((uint32_t)lane < fl_n && (w & RH_ACTIVE) != 0u, fl_i, w);
@@ -971,8 +935,8 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
                 // (everything this wave has requested is there: the bits of the contacts in flight too)
                 if (C.fl) resolve_finish(P, T, B, S, S_pressure, uniform_meta, dp, (C.cur ^ 1u) * 64u, C);
             }
-            PROF_END(14);
-            PROF_BEGIN(15);
+            PROF_END(SPARSE_WORDS);
+            PROF_BEGIN(SPARSE_BITS);
             // (the lane's 128 bits as two 64-bit halves, the lowest set bit of the lower non-empty half taken each step: straight-line
             // code -- as four words with a four-way choice of the word to take from and to write back, the compiler's version of
             // this loop was 75 instructions under three nested exec masks, a fifth of the wave's peak-day cycles)
@@ -981,9 +945,9 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
                 while (!__any(have) && sp_k < sp_chunks) {
                     const uint32_t set = sp_k % SP_SETS;
                     uint4 bw;
-                    PROF_BEGIN(3);
+                    PROF_BEGIN(BITS_WAIT);
                     SP_TAKE(bw, set);
-                    PROF_END(3);
+                    PROF_END(BITS_WAIT);
                     if (sp_k * 16u + ((uint32_t)lane >> 2) >= my_tiles) bw = make_uint4(0, 0, 0, 0);   // (a lane past the wave's last tile loaded word 0)
                     if (sp_k + SP_SETS < sp_chunks) SP_ISSUE(set, sp_k + SP_SETS);
                     b_lo = (uint64_t)bw.x | ((uint64_t)bw.y << 32);
@@ -994,10 +958,7 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
                     have = (b_lo | b_hi) != 0ull;
                 }
                 if (!__any(have)) break;
-#if defined(REINA_DAY_PROF) && REINA_DAY_PROF == 17   // iterations of the bit loop (prof_n_) and lanes that took a bit in them (prof_t_)
-                prof_n_++;
-                prof_t_ += (uint32_t)__popcll(__ballot(have));
-#endif
+                PROF_TALLY(BIT_LANES, 1u, (uint32_t)__popcll(__ballot(have)));
                 const bool up = b_lo == 0ull;
                 const uint64_t word = up ? b_hi : b_lo;
                 const uint32_t w_lo = (uint32_t)word, w_hi = (uint32_t)(word >> 32);
@@ -1013,8 +974,8 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
                 iqn += (uint32_t)__popcll(m);
                 have = (b_lo | b_hi) != 0ull;
             }
-            PROF_END(15);
-            PROF_BEGIN(16);
+            PROF_END(SPARSE_BITS);
+            PROF_BEGIN(SPARSE_FETCH);
             const bool bits_left = __any(have) || sp_k < sp_chunks;
             if (!fl_n && iqn >= (bits_left ? 64u : 1u)) {
                 fl_n = iqn < 64u ? iqn : 64u;
@@ -1027,7 +988,7 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
                 }
             }
             more = bits_left || iqn > 0u || fl_n > 0u;
-            PROF_END(16);
+            PROF_END(SPARSE_FETCH);
         } else {
             // A dense day: the tile's words are in register set `cur`; its need bits are queued word slot by word slot (at
             // most 64 agents a step) until a state-machine round is due, then the set is requested again, three tiles ahead.
@@ -1100,7 +1061,7 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
             // workgroup's finish from 72.9 to 70.9 us; the launch did not get shorter, the peak day got 5 % longer.  The tail of
             // the stream is not where the bandwidth is lost.)
         }
-        PROF_END(1);
+        PROF_END(FEED);
 #ifndef REINA_NO_DAY_PRIO
         __builtin_amdgcn_s_setprio(2);
 #endif
@@ -1113,7 +1074,7 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
                 L.qn -= n;
                 __builtin_amdgcn_s_waitcnt(0xc07f);
                 __builtin_amdgcn_wave_barrier();
-                PROF_BEGIN(5);
+                PROF_BEGIN(BATCHES);
 #ifndef REINA_NO_DAY_PRIO
                 __builtin_amdgcn_s_setprio(1);   // (the batch's head; its steps go on at 0: contact_batch)
 #endif
@@ -1121,7 +1082,7 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
 #ifndef REINA_NO_DAY_PRIO
                 __builtin_amdgcn_s_setprio(2);
 #endif
-                PROF_END(5);
+                PROF_END(BATCHES);
                 continue;
             }
             if (nqn >= (more ? 64u : 1u)) {
@@ -1129,10 +1090,8 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
                 nqn -= n;
                 __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the wave-private queue is written
                 __builtin_amdgcn_wave_barrier();
-#if defined(REINA_DAY_PROF) && REINA_DAY_PROF == 13   // what the feeder left in flight
-                PROF_BEGIN(13); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); PROF_END(13);
-#endif
-                PROF_BEGIN(4);
+                PROF_DRAINED(FEED_DRAIN);
+                PROF_BEGIN(ROUNDS);
                 const bool valid = (uint32_t)lane < n;
                 const uint2 q = valid ? nq[nqn + lane] : make_uint2(0u, 0u);
                 // (bed / ICU events: staged in LDS while the stream runs, straight to their buckets from the rounds that drain the
@@ -1140,20 +1099,18 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
                 // a round trip on every workgroup's way out)
                 const uint32_t nw = scan_word(P, B, L, valid, q.x, q.y, dp.day, &S.ev_n, S.ev_key, more ? DAY_EV_STAGE : 0u, S.var_par);
                 // a deferred (onset) word keeps its old value here and is written by become_ill
-                if (valid && nw != q.y && !ABLATED(32u)) B.hot[q.x] = nw;
-                PROF_END(4);
-#if defined(REINA_DAY_PROF) && REINA_DAY_PROF == 12   // what a state-machine round leaves in flight
-                PROF_BEGIN(12); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); PROF_END(12);
-#endif
+                if (valid && nw != q.y && !ABLATED(HOT_STORE)) B.hot[q.x] = nw;
+                PROF_END(ROUNDS);
+                PROF_DRAINED(ROUND_DRAIN);
                 continue;
             }
             break;
         }
         if (!more) break;
     }
-    DSTAMP(1);
-    PROF_END(0);
-    PROF_BEGIN(7);
+    DIAG_SINCE(DAY, DIAG_DAY_STREAM, DIAG_THREAD0, ds_t0, B.mirror);
+    PROF_END(LOOP);
+    PROF_BEGIN(TAIL);
     // the wave's last pending contacts: the batch in flight, then the fewer than 64 of the region being filled
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
@@ -1163,17 +1120,8 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
         resolve_finish(P, T, B, S, S_pressure, uniform_meta, dp, C.cur * 64u, C);
     }
     asm volatile("s_waitcnt vmcnt(0)" : : : "memory");   // (the loads past the end that were never looked at)
-    PROF_END(7);
-#ifdef REINA_DAY_PROF
-    if (lane == 0) {
-        if (REINA_DAY_PROF == 6 || (REINA_DAY_PROF >= 8 && REINA_DAY_PROF <= 11)) { prof_t_ = C.prof_in; prof_n_ = C.prof_in_n; }
-// one row of plain stores per wave (buffers.mirror of an unsharded engine is scratch with room for 8192 rows): sums by
-        // same-address atomics, as until round 4, took 8.5 ns each in L2 -- 140 us for a launch's 16 384, a quiet day's kernel
-        // measured at 160 us instead of 21, and every wave's stores queued behind them
-        GAS uint64_t *row_ = B.mirror + 64 + (size_t)wave_global * 4u;
-        row_[0] = prof_all_; row_[1] = prof_t_; row_[2] = prof_n_; row_[3] = 1ull;
-    }
-#endif
+    PROF_END(TAIL);
+    PROF_WRITE_ROW(B.mirror, wave_global, C);
 #undef DAY_PUSH
 #undef DAY_WORD
 #undef DAY_WORD_REG
@@ -1189,22 +1137,19 @@ __device__ __forceinline__ void day_block(const MemberRef &mref_, const reina_da
         const uint32_t c = lane == 0 ? (C.n_cand < C.slice_cap ? C.n_cand : C.slice_cap) : lane == 1 ? L.n[1] : lane == 2 ? 0u : L.n[3];
         B.work_counts[(lane == 0 ? LIST_CAND : lane) * REINA_MAX_SCAN_WAVES + wave_global] = c;
     }
-    DSTAMP(2);
+    DIAG_SINCE(DAY, DIAG_DAY_RESOLVED, DIAG_THREAD0, ds_t0, B.mirror);
     flush_places(S.daily, (uint32_t)C.pl & 0x3FFFFFFFu, (uint32_t)(C.pl >> 30) & 0x3FFFFFFFu);
     if (lane == 0 && C.wave_contacts) atomicAdd(&S.n_contacts, (int)C.wave_contacts);
     if (lane == 0 && n_act) atomicAdd(&S.n_active, (int)n_act);
     if (lane == 0 && L.n_hosp) atomicAdd(&S.n_hosp, (int)L.n_hosp);   // (the day's admission / transfer requests: hosp_day_is_ordered)
     if (lane == 0 && L.n_icu) atomicAdd(&S.n_icu, (int)L.n_icu);
     __syncthreads();
-    DSTAMP(3);
-#ifdef REINA_DAY_STAMPS
-    if (tid == 0) atomicAdd((unsigned long long *)&B.mirror[60], 1ull);
-#endif
+    DIAG_SINCE(DAY, DIAG_DAY_BARRIER, DIAG_THREAD0, ds_t0, B.mirror);
     // the workgroup's staged bed / ICU events go to their priority buckets: one returning atomic per event, all of them in
     // flight together (rounds 1-3: one in the middle of every state-machine round that found an event)
     {
         const uint32_t n_ev = S.ev_n < DAY_EV_STAGE ? S.ev_n : DAY_EV_STAGE;
-        for (uint32_t k = (uint32_t)tid; k < (ABLATED(128u) ? 0u : n_ev); k += DAY_THREADS) hosp_push_key(P, B, S.ev_key[k]);
+        for (uint32_t k = (uint32_t)tid; k < (ABLATED(EVENT_PUSH) ? 0u : n_ev); k += DAY_THREADS) hosp_push_key(P, B, S.ev_key[k]);
     }
     // The workgroup's sums, in TWO vector instructions: an atomic instruction occupies the L2 line it addresses for some 12 ns
     // whatever the number of its lanes and words (tools/ubench_atomics.hip), and the control words of a day share one line, its

@@ -151,12 +151,6 @@ __device__ __forceinline__ void hosp_sort_wave(uint64_t *seg, int n, int lane) {
         if (lane * E + r < n) seg[lane * E + r] = x[r];
 }
 
-#ifdef REINA_HOSP_STAMPS
-// diagnostic: per-phase time of the event walk accumulated in buffers.mirror[0..7] (100 MHz ticks)
-#define HSTAMP(k) do { if (threadIdx.x == 0) { uint64_t t_ = wall_clock64(); atomicAdd((unsigned long long *)&B.mirror[k], (unsigned long long)(t_ - hs_t)); hs_t = t_; } } while (0)
-#else
-#define HSTAMP(k) do { } while (0)
-#endif
 
 // One bed / ICU event applied to its agent: person_hospitalize / transfer_to_icu / release_from_hospital
 // (main.pyx:321-367).  `w`, `od`: the agent's hot word and onset-to-removed duration; `granted`: the bed / ICU
@@ -337,9 +331,7 @@ __device__ __forceinline__ void hospital_block(const MemberRef &mref_, const rei
     __shared__ int32_t s_age_start[REINA_MAX_AGES + 1];
     // (a population this walk serves has at most HOSP_SMALL_RANGES buckets: one per 65 536 agents, include/reina_hip.h)
     __shared__ uint32_t s_base[HOSP_SMALL_RANGES + 1];               // exclusive prefix of the bucket counts
-#ifdef REINA_HOSP_STAMPS
-    uint64_t hs_t = wall_clock64();
-#endif
+    DIAG_CLOCK(HOSP, hs_t);   // (-DREINA_HOSP_STAMPS: the walk's phases, reina_diag.h)
     const int tid = threadIdx.x;
     const uint32_t R = P->hosp_ranges, C = P->hosp_bucket_cap;
     __shared__ uint32_t s_n[HOSP_SMALL_RANGES];
@@ -377,7 +369,7 @@ __device__ __forceinline__ void hospital_block(const MemberRef &mref_, const rei
         ev[p0] = hosp_bucket(P, B, lo)[(uint32_t)p0 - s_base[lo]];
     }
     __syncthreads();
-    HSTAMP(1);
+    DIAG_LAP(HOSP, DIAG_HOSP_GATHER, DIAG_THREAD0, hs_t, B.mirror);
     // The buckets are in priority order among themselves.  Usual day: no bucket holds more than 256 keys, and every bucket
     // is sorted by one wave on its own (registers + shuffles, no barrier), two buckets per wave.  Otherwise: runs of whole
     // buckets holding at most 1024 keys are sorted one after the other by the workgroup's network.
@@ -419,20 +411,20 @@ __device__ __forceinline__ void hospital_block(const MemberRef &mref_, const rei
         }
         r0 = r1;
     }
-    HSTAMP(3);
+    DIAG_LAP(HOSP, DIAG_HOSP_SORT, DIAG_THREAD0, hs_t, B.mirror);
     int b_end, c_end;
     const int b0 = B.control[REINA_L_BEDS_OPEN], c0 = B.control[REINA_L_ICU_OPEN];
     hosp_decide<HOSP_THREADS>(ev, M, b0, c0, s_f[0], s_f[1], &b_end, &c_end);
-    HSTAMP(4);
+    DIAG_LAP(HOSP, DIAG_HOSP_DECIDE, DIAG_THREAD0, hs_t, B.mirror);
     hosp_apply_all<HOSP_THREADS>(P, B, dp, s_age_start, s_cnt, ev, M);
     __syncthreads();
-    HSTAMP(5);
+    DIAG_LAP(HOSP, DIAG_HOSP_APPLY, DIAG_THREAD0, hs_t, B.mirror);
     hosp_flush_counts(B, s_cnt, HOSP_THREADS);
     if (tid == 0) {
         B.counters[SC_IDX(REINA_S_AVAILABLE_BEDS)] = b_end;
         B.counters[SC_IDX(REINA_S_AVAILABLE_ICU)] = c_end;
     }
-    HSTAMP(6);
+    DIAG_LAP(HOSP, DIAG_HOSP_FLUSH, DIAG_THREAD0, hs_t, B.mirror);
 }
 
 // ---------------------------------------------------------------------------------------------

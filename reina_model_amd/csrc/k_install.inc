@@ -87,15 +87,11 @@ __device__ __forceinline__ void install_block(const MemberRef &mref_, const rein
     if (threadIdx.x < REINA_MAX_AGES) new_by_age[threadIdx.x] = 0;
     if (threadIdx.x < REINA_MAX_VARIANTS) new_by_variant[threadIdx.x] = 0;
     if (threadIdx.x == 0 && stage) stage->n = 0;
-#ifdef REINA_INSTALL_STAMPS
-    uint64_t is_t = wall_clock64();
-    const int is_role = only_events ? 8 : 0;   // [sum 0..2, -, max 4..6, -] main workgroups, [8..] the events-only workgroup
-#define ISTAMP(k) do { __syncthreads(); if (threadIdx.x == 0) { uint64_t t_ = wall_clock64(); atomicAdd((unsigned long long *)&B.mirror[is_role + (k)], (unsigned long long)(t_ - is_t)); atomicMax((unsigned long long *)&B.mirror[is_role + 4 + (k)], (unsigned long long)(t_ - is_t)); is_t = t_; } } while (0)
-#else
-#define ISTAMP(k) do { } while (0)
-#endif
+    DIAG_CLOCK(INSTALL, is_t);   // (-DREINA_INSTALL_STAMPS: the phases of the two roles, each under its own names)
+#define INSTALL_LAP(ph) do { if (only_events) DIAG_LAP(INSTALL, DIAG_INSTALL_EVENTS_##ph, DIAG_BARRIER_THREAD0, is_t, B.mirror); \
+                             else DIAG_LAP(INSTALL, DIAG_INSTALL_MAIN_##ph, DIAG_BARRIER_THREAD0, is_t, B.mirror); } while (0)
     __syncthreads();
-    ISTAMP(0);
+    INSTALL_LAP(SETUP);
     const GAS uint4 *cand = reinterpret_cast<const GAS uint4 *>(B.candidates);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t cap = P->max_work_items;
@@ -254,7 +250,7 @@ __device__ __forceinline__ void install_block(const MemberRef &mref_, const rein
         }
     }
     if (stage && !only_events) onset_stage_flush(P, B, stage, (dp.day & 1) ^ 1);   // the workgroup's appends to tomorrow's test queue
-    ISTAMP(1);
+    INSTALL_LAP(WORK);
     // tomorrow's mirror-table sizes: about twice this shard's share of today's cross-shard attempts of
     // the cell (buffers.pressure holds the sums over all shards by now), a power of two in [8, mirror_slots]
     if (P->n_shards > 1 && !IS_EXACT(P) && !only_events && bx == 0 && threadIdx.x < REINA_MIRROR_CELLS) {
@@ -307,7 +303,8 @@ __device__ __forceinline__ void install_block(const MemberRef &mref_, const rein
             for (int q = 0; q < 4; q++) B.control[REINA_L_IMPORT_SYNC + q] = 0;   // (and the arrival words of its import workgroups)
         }
     }
-    ISTAMP(2);
+    INSTALL_LAP(FLUSH);
+#undef INSTALL_LAP
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -348,18 +345,9 @@ DAY_KERNEL __launch_bounds__(HOSP_THREADS) void k_hosp_install(const MemberRef *
     // chip, R / 16 = 64 of 256 CUs at 10^8 agents, stood idle through the installs of every day on which nothing ran out)
     if (flags & HI_HOSP_WG) {
         if (bx == 0 && ordered) {
-#ifdef REINA_HOSP_STAMPS
-            const uint64_t hb_t = wall_clock64();
-#endif
+            DIAG_CLOCK(HOSP, hb_t);
             hospital_block(mref_, dp, s_hl, s_f);
-#ifdef REINA_HOSP_STAMPS
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                GAS uint64_t *mir = (GAS uint64_t *)mref_.B.mirror;
-                atomicAdd((unsigned long long *)&mir[7], (unsigned long long)(wall_clock64() - hb_t));
-                atomicAdd((unsigned long long *)&mir[8], 1ull);
-            }
-#endif
+            DIAG_SINCE(HOSP, DIAG_HOSP_BLOCK, DIAG_BARRIER_THREAD0, hb_t, mref_.B.mirror);
             return;
         }
         if (flags & HI_INSTALL) {

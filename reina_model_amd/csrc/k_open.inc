@@ -147,12 +147,7 @@ __device__ void pro_imports(const CAS DevParams *P, const GBuffers &B, const rei
                             uint32_t *import_base, uint8_t *placed, uint32_t *s_unplaced,
                             int32_t *new_by_age, int32_t *new_by_variant, const int32_t *s_age_start, const ImportClasses *ic,
                             uint32_t &phase, bool wait_for_open = false, uint32_t r = 0, uint32_t W = 1, bool deferred = false) {
-#ifdef REINA_OPEN_STAMPS
-    uint64_t ip_t = wall_clock64();
-#define IPSTAMP(k) do { if (threadIdx.x == 0 && wait_for_open && r == 0) { const uint64_t t_ = wall_clock64(); atomicAdd((unsigned long long *)&B.mirror[48 + (k)], (unsigned long long)(t_ - ip_t)); ip_t = t_; } } while (0)
-#else
-#define IPSTAMP(k) do { } while (0)
-#endif
+    DIAG_CLOCK(IMPORTS, ip_t);   // (-DREINA_OPEN_STAMPS: the placement's phases in the weekly-import workgroup, helper 0)
     uint32_t total = 0;
     for (uint32_t b = 0; b < dp.n_import_batches; b++)
         if ((int)dp.import_batches[b].pre_init == pre_init) total += dp.import_batches[b].count;
@@ -175,7 +170,7 @@ __device__ void pro_imports(const CAS DevParams *P, const GBuffers &B, const rei
         __syncthreads();
         for (uint32_t sl = threadIdx.x; sl < PRO_MAX_IMPORTS && IMPORT_OF_SLOT(sl) < n; sl += PRO_THREADS) placed[sl] = 0;
         __syncthreads();
-        IPSTAMP(0);
+        DIAG_LAP(IMPORTS, DIAG_IMPORTS_SETUP, DIAG_THREAD0, ip_t, B.mirror, wait_for_open && r == 0);
         for (;;) {
             int proposals = 0;
             for (uint32_t sl = threadIdx.x; sl < PRO_MAX_IMPORTS; sl += PRO_THREADS) {
@@ -202,9 +197,9 @@ __device__ void pro_imports(const CAS DevParams *P, const GBuffers &B, const rei
                 }
                 placed[sl] = (uint8_t)(k < 10 ? (0x80u | k) : 10u);
             }
-            IPSTAMP(1);
+            DIAG_LAP(IMPORTS, DIAG_IMPORTS_PROPOSE, DIAG_THREAD0, ip_t, B.mirror, wait_for_open && r == 0);
             if (!imports_any(B, r, W, phase, proposals)) break;
-            IPSTAMP(2);
+            DIAG_LAP(IMPORTS, DIAG_IMPORTS_ANY_PROPOSED, DIAG_THREAD0, ip_t, B.mirror, wait_for_open && r == 0);
             int evicted = 0;
             for (uint32_t sl = threadIdx.x; sl < PRO_MAX_IMPORTS; sl += PRO_THREADS) {
                 const uint32_t j = IMPORT_OF_SLOT(sl);
@@ -218,10 +213,10 @@ __device__ void pro_imports(const CAS DevParams *P, const GBuffers &B, const rei
                     evicted++;
                 }
             }
-            IPSTAMP(3);
+            DIAG_LAP(IMPORTS, DIAG_IMPORTS_VERIFY, DIAG_THREAD0, ip_t, B.mirror, wait_for_open && r == 0);
             if (!imports_any(B, r, W, phase, evicted)) break;
         }
-        IPSTAMP(4);
+        DIAG_LAP(IMPORTS, DIAG_IMPORTS_LEFT_ROUNDS, DIAG_THREAD0, ip_t, B.mirror, wait_for_open && r == 0);
         // every holder's target is its own: infect
         for (uint32_t sl = threadIdx.x; sl < PRO_MAX_IMPORTS; sl += PRO_THREADS) {
             const uint32_t j = IMPORT_OF_SLOT(sl);
@@ -257,7 +252,7 @@ __device__ void pro_imports(const CAS DevParams *P, const GBuffers &B, const rei
             }
             placed[sl] = 255;
         }
-        IPSTAMP(5);
+        DIAG_LAP(IMPORTS, DIAG_IMPORTS_INFECT, DIAG_THREAD0, ip_t, B.mirror, wait_for_open && r == 0);
         __syncthreads();
         for (uint32_t sl = threadIdx.x; sl < PRO_MAX_IMPORTS; sl += PRO_THREADS) {
             if (IMPORT_OF_SLOT(sl) >= n) break;
@@ -267,10 +262,10 @@ __device__ void pro_imports(const CAS DevParams *P, const GBuffers &B, const rei
     if (threadIdx.x == 0) *s_unplaced = 0;
     // agents are placed; the counters follow the daily zeroing (a wait that gave up has flagged the day
     // failed: the counters, possibly not zeroed yet, are then left alone)
-    IPSTAMP(6);
+    DIAG_LAP(IMPORTS, DIAG_IMPORTS_TAIL, DIAG_THREAD0, ip_t, B.mirror, wait_for_open && r == 0);
     const bool counters_open = !wait_for_open || wait_day_open(B, dp.day);
     __syncthreads();
-    IPSTAMP(7);
+    DIAG_LAP(IMPORTS, DIAG_IMPORTS_WAIT_OPEN, DIAG_THREAD0, ip_t, B.mirror, wait_for_open && r == 0);
     if (mine) atomicAdd(s_unplaced, mine);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -281,7 +276,7 @@ __device__ void pro_imports(const CAS DevParams *P, const GBuffers &B, const rei
     // shared intervention imports: the opening workgroup goes on to zero the day's counters only when every helper's
     // counts are in
     if (W > 1 && pre_init) imports_any(B, r, W, phase, 0);
-    IPSTAMP(8);
+    DIAG_LAP(IMPORTS, DIAG_IMPORTS_FLUSH, DIAG_THREAD0, ip_t, B.mirror, wait_for_open && r == 0);
 }
 
 // HealthcareSystem.vaccinate_people (main.pyx:560-583): oldest first from a persistent cursor.
@@ -625,9 +620,7 @@ __device__ __forceinline__ void prologue_block(const MemberRef &mref_, const rei
     uint32_t &s_unplaced = OL.s_unplaced, &s_import_base = OL.s_import_base;
     int32_t *new_by_age = OL.new_by_age, *new_by_variant = OL.new_by_variant, *s_age_start = OL.s_age_start;
     const int tid = threadIdx.x;
-#ifdef REINA_OPEN_STAMPS
-    const uint64_t ps_t = wall_clock64();
-#endif
+    DIAG_CLOCK(OPEN, ps_t);
     if (tid <= REINA_MAX_AGES) s_age_start[tid] = P->age_start[tid];
     if (tid < REINA_MAX_AGES) new_by_age[tid] = 0;
     if (tid < REINA_MAX_VARIANTS) new_by_variant[tid] = 0;
@@ -704,18 +697,14 @@ __device__ __forceinline__ void prologue_block(const MemberRef &mref_, const rei
         B.pressure[REINA_PRESSURE_FREE_ICU(P->shard_rank)] = pre_aicu + dp.add_icu_units;
     }
     if (tid == 0) __hip_atomic_store(&B.control[REINA_L_DAY_OPEN], (int32_t)dp.day + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef REINA_OPEN_STAMPS
-    if (tid == 0) atomicAdd((unsigned long long *)&B.mirror[5], (unsigned long long)(wall_clock64() - ps_t));
-#endif
+    DIAG_SINCE(OPEN, DIAG_OPEN_UNTIL_FLAG, DIAG_THREAD0, ps_t, B.mirror);
     // weekly imports (Population.infect_people_daily, main.pyx:1671-1685) run after init_day's
     // zeroing; vaccination follows the test-queue pass in the reference (main.pyx:547-558) and is
     // launched from k_vaccinate after both.
     __syncthreads();
     if (!weekly_elsewhere)
         pro_imports(P, B, dp, 0, &s_import_base, placed, &s_unplaced, new_by_age, new_by_variant, s_age_start, &OL.classes, phase, false, 0, W);
-#ifdef REINA_OPEN_STAMPS
-    if (tid == 0) atomicAdd((unsigned long long *)&B.mirror[6], (unsigned long long)(wall_clock64() - ps_t));
-#endif
+    DIAG_SINCE(OPEN, DIAG_OPEN_TOTAL, DIAG_THREAD0, ps_t, B.mirror);
 }
 
 // The weekly imports in a workgroup of their own (days without intervention imports, whose claim
@@ -738,16 +727,12 @@ __device__ __forceinline__ void weekly_imports_block(const MemberRef &mref_, con
     if (tid < REINA_MAX_VARIANTS) new_by_variant[tid] = 0;
     if (tid == 0) s_import_base = 0;
     __syncthreads();
-#ifdef REINA_OPEN_STAMPS
-    const uint64_t ws_t = wall_clock64();
-#endif
+    DIAG_CLOCK(OPEN, ws_t);
     import_classes_load(P, s_age_start, &OL.classes);
     uint32_t phase = 0;
     if (with_opening) pro_imports(P, B, dp, 1, &s_import_base, placed, &s_unplaced, new_by_age, new_by_variant, s_age_start, &OL.classes, phase, false, r, W);
     pro_imports(P, B, dp, 0, &s_import_base, placed, &s_unplaced, new_by_age, new_by_variant, s_age_start, &OL.classes, phase, !with_opening, r, W);
-#ifdef REINA_OPEN_STAMPS
-    if (tid == 0 && r == 0) atomicAdd((unsigned long long *)&B.mirror[9], (unsigned long long)(wall_clock64() - ws_t));
-#endif
+    DIAG_SINCE(OPEN, DIAG_OPEN_WEEKLY, DIAG_THREAD0, ws_t, B.mirror, r == 0);
 }
 
 // ... and in k_day's launch (`deferred`, above): workgroup r of the W that follow the streaming workgroups

@@ -14,12 +14,6 @@
 //   symptom onsets       -> per-wave slice in HBM -> k_hosp_install (gamma draw of the illness course, testing decision)
 //   hospital events      -> the day's priority buckets in HBM (k_hospital.inc) -> k_hosp_install / k_hosp_sort + k_hosp_walk
 //   bookkeeping          -> per-wave slice in HBM -> k_hosp_install (R statistics, recovered / died-at-home counters)
-#ifdef REINA_ABLATE   // diagnostic builds (tools/ablate_day.py): parts of k_day switched off at run time, for timing only
-__device__ uint32_t g_ablate_dev;
-#define ABLATED(bit) (g_ablate_dev & (bit))
-#else
-#define ABLATED(bit) false
-#endif
 #define DAY_EV_STAGE 1024   // bed / ICU events a workgroup of k_day stages in LDS before they go to their buckets
 enum { SL_INFECTED = 0, SL_RECOVERED, SL_DEAD, SL_NHD, SL_NR };
 enum { LIST_EXP = 0, LIST_ILL = 1, LIST_EV = 2, LIST_BOOK = 3, LIST_CAND = 4 };
@@ -40,7 +34,7 @@ __device__ __forceinline__ uint32_t onset_word(const CAS DevParams *P, const GBu
     int v = RH_VARIANT(w), sev = RH_SEV(w);
     float mu = sev == RV_FATAL ? d.mean_duration_from_onset_to_death[v] : d.mean_duration_from_onset_to_recovery[v];
     float od = rp_gamma_mu_cv(mu, 0.45f, P->k0, P->k1, i, day, RP_P_ONSET, 1);
-    if (!ABLATED(64u)) B.cold[i].onset_days = od;
+    if (!ABLATED(ONSET_STORE)) B.cold[i].onset_days = od;
     float f = od;
     if (sev >= RV_SEVERE) f *= d.ratio_of_duration_before_hospitalisation[v];
     w = RH_SET_STATE(w, RS_ILLNESS);
@@ -130,7 +124,7 @@ struct ScanLists {
 
 __device__ __forceinline__ void list_push(ScanLists &L, int which, bool pred, uint32_t x, uint32_t y) {
     const uint64_t m = __ballot(pred);
-    if (pred && !ABLATED(16u)) gst(&L.l[which][L.n[which] + (uint32_t)__popcll(m & ((1ull << lane_id()) - 1ull))], make_uint2(x, y));
+    if (pred && !ABLATED(LIST_STORES)) gst(&L.l[which][L.n[which] + (uint32_t)__popcll(m & ((1ull << lane_id()) - 1ull))], make_uint2(x, y));
     L.n[which] += (uint32_t)__popcll(m);
 }
 __device__ __forceinline__ void strip_push(ScanLists &L, bool pred, uint32_t x, uint32_t y) {
@@ -151,7 +145,7 @@ __device__ __forceinline__ uint32_t scan_word(const CAS DevParams *P, const GBuf
         if (st >= RS_RECOVERED) {
             // removed, not yet counted into R (main.pyx:1969-1972): mark; n_infected is gathered later
             nw = (w | RH_INCLUDED) & ~RH_ACTIVE;
-            if (!ABLATED(8u)) agent_bit_clear(B.active_bits, i);   // (the plane that says the same thing: k_day's sparse days stream it)
+            if (!ABLATED(ACTIVE_CLEAR)) agent_bit_clear(B.active_bits, i);   // (the plane that says the same thing: k_day's sparse days stream it)
             p_bk = true;
             kind = EVX_COUNT_R;
         } else if (RH_INFECTED_TODAY(w, day)) {

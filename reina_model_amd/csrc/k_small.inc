@@ -108,14 +108,7 @@ __global__ __launch_bounds__(HOSP_THREADS) void k_small_days(MemberRef one_, Sma
     int32_t (*s_hl)[REINA_MAX_AGES] = reinterpret_cast<int32_t (*)[REINA_MAX_AGES]>(smem_sd + SMALL_HL_OFF);
     const uint32_t scan_waves = (W - 1u) * DAY_WAVES;
     uint32_t nb = g.bar_base;
-#ifdef REINA_SMALL_STAMPS   // diagnostic builds (tools/small_stamps.py): every workgroup's time in each phase, summed and the longest, in buffers.mirror[100..]
-    uint64_t ss_t = wall_clock64();
-#define SSTAMP(k) do { __syncthreads(); if (threadIdx.x == 0) { const uint64_t t_ = wall_clock64(); GAS uint64_t *m_ = (GAS uint64_t *)one_.B.mirror; \
-        atomicAdd((GAS unsigned long long *)&m_[100 + (k)], (unsigned long long)(t_ - ss_t)); atomicMax((GAS unsigned long long *)&m_[110 + (k)], (unsigned long long)(t_ - ss_t)); \
-        if ((k) == 0) atomicAdd((GAS unsigned long long *)&m_[120], 1ull); ss_t = t_; } } while (0)
-#else
-#define SSTAMP(k) do { } while (0)
-#endif
+    DIAG_CLOCK(SMALL, ss_t);   // (-DREINA_SMALL_STAMPS: every workgroup's time in each phase of a day, summed and the longest)
     for (uint32_t d = 0; d < g.n_days; d++) {
         // (the parameter block and the tables are constants: left alone, the compiler reads everything the three phases will ever ask
         // of them in front of this loop and carries it through -- 118 registers in scratch.  A day's phases get their pointers
@@ -129,18 +122,18 @@ __global__ __launch_bounds__(HOSP_THREADS) void k_small_days(MemberRef one_, Sma
         const uint32_t stream_imports = recs[d].stream_imports;
         // phase 1, the day's opening: role = workgroup number (the launch is resident as a whole: no tickets)
         open_role<false>(mref_, dp, 0u, weekly_own, mode, bx, W, ovl);
-        SSTAMP(0);
+        DIAG_LAP(SMALL, DIAG_SMALL_OPENING, DIAG_BARRIER_THREAD0, ss_t, one_.B.mirror);
         small_day_barrier(bar, ++nb * W, counters);
-        SSTAMP(1);
+        DIAG_LAP(SMALL, DIAG_SMALL_BARRIER1, DIAG_BARRIER_THREAD0, ss_t, one_.B.mirror);
         // phase 2, the stream + contact sampling on workgroups 1..; the control workgroup places the weekly imports beside it
         if (bx == 0) {
             if (stream_imports) day_imports_block(mref_, dp, smem_sd, 0u, 1u);
         } else {
             day_block<false, FEED_PLAIN>(mref_, dp, g.lds_rows, g.lds_crows, g.day_flags, 0u, bx - 1u, W - 1u, smem_sd, d != 0u);
         }
-        SSTAMP(2);
+        DIAG_LAP(SMALL, DIAG_SMALL_STREAM, DIAG_BARRIER_THREAD0, ss_t, one_.B.mirror);
         small_day_barrier(bar, ++nb * W, counters);
-        SSTAMP(3);
+        DIAG_LAP(SMALL, DIAG_SMALL_BARRIER2, DIAG_BARRIER_THREAD0, ss_t, one_.B.mirror);
         // phase 3, k_hosp_install's small shape: the control workgroup has the bed / ICU events (the ordered walk, or all granted),
         // the others install
         if (bx == 0) {
@@ -149,10 +142,9 @@ __global__ __launch_bounds__(HOSP_THREADS) void k_small_days(MemberRef one_, Sma
         } else {
             install_block<false>(mref_, dp, scan_waves, g.scan_tiles, bx - 1u, W - 1u, false, false, s_hl, reinterpret_cast<OnsetStage *>(ovl));
         }
-        SSTAMP(4);
+        DIAG_LAP(SMALL, DIAG_SMALL_INSTALLS, DIAG_BARRIER_THREAD0, ss_t, one_.B.mirror);
         // (the next day's opening reads what the installs wrote: tomorrow's test queue, the counters of the snapshot)
         small_day_barrier(bar, ++nb * W, counters);
-        SSTAMP(5);
+        DIAG_LAP(SMALL, DIAG_SMALL_BARRIER3, DIAG_BARRIER_THREAD0, ss_t, one_.B.mirror);
     }
-#undef SSTAMP
 }

@@ -66,11 +66,6 @@ __device__ __forceinline__ bool try_queue(const CAS DevParams *P, const GBuffers
 // Level 0 also performs the detection of its queue entry (k_test_detect's job) in the same pass:
 // every member of today's queue carries QUEUED until its single store replaces it with DETECTED,
 // so a tracer can never re-queue another member, whichever of the two runs first.
-#ifdef REINA_OPEN_STAMPS
-#define OSTAMP(k) do { if (threadIdx.x == 0) { uint64_t t_ = wall_clock64(); atomicAdd((unsigned long long *)&B.mirror[k], (unsigned long long)(t_ - os_t)); atomicMax((unsigned long long *)&B.mirror[16 + (k)], (unsigned long long)(t_ - os_t)); atomicAdd((unsigned long long *)&B.mirror[24 + (k)], 1ull); os_t = t_; } } while (0)
-#else
-#define OSTAMP(k) do { } while (0)
-#endif
 #define TRACE_STAGE 4096
 // successes of a workgroup are staged in LDS and appended to the global lists with ONE allocation
 // per list at the end (a returning global atomic per success would sit in every lane's dependent
@@ -120,26 +115,19 @@ __device__ __forceinline__ void test_trace_block(const MemberRef &mref_, const r
     // only so many misses in flight.)  A short list stays with one workgroup, which then walks level 1 without a fence.
     const uint32_t ch_sh = (uint32_t)n > blockDim.x ? 6u : (uint32_t)__builtin_ctz(blockDim.x), ch = 1u << ch_sh;   // (block sizes are powers of two)
     if (n <= (int)(bx * ch)) return;
-#ifdef REINA_OPEN_STAMPS
-    uint64_t os_t = wall_clock64();
-#endif
+    DIAG_CLOCK(OPEN, os_t);   // (-DREINA_OPEN_STAMPS: this workgroup's phases, and its slowest wave's way through an entry)
     if (LEVEL == 0) {
         if (threadIdx.x <= REINA_MAX_AGES) s_age_start[threadIdx.x] = P->age_start[threadIdx.x];
         if (threadIdx.x < REINA_MAX_AGES) s_det[threadIdx.x] = 0;
     }
     if (threadIdx.x == 0) S.n = 0;
     __syncthreads();
-#ifdef REINA_OPEN_STAMPS
-#define TSTAMP(slot) do { if ((threadIdx.x & 63) == 0) atomicMax((unsigned long long *)&B.mirror[(LEVEL ? 44 : 40) + (slot)], (unsigned long long)(wall_clock64() - os_t)); } while (0)
-#else
-#define TSTAMP(slot) do { } while (0)
-#endif
     for (uint32_t c = bx + nbx * (threadIdx.x >> ch_sh);; c += nbx * (blockDim.x >> ch_sh)) {
         const uint32_t k = c * ch + (threadIdx.x & (ch - 1u));
         if (c * ch >= (uint32_t)n) break;     // (uniform over a chunk: a wave leaves the loop as one)
         if (k >= (uint32_t)n) continue;
         const uint32_t i = src[k];
-        TSTAMP(0);
+        DIAG_SINCE(TRACE, LEVEL ? DIAG_TRACE_L1_ENTRY : DIAG_TRACE_L0_ENTRY, DIAG_WAVE_LANE0, os_t, B.mirror);
         // everything that depends only on i is requested together: its word, its record (infector, head of the overflow
         // list) and its block of inline infectee slots -- three accesses, one round trip
         const int32_t inf = B.cold[i].infector;
@@ -171,7 +159,7 @@ __device__ __forceinline__ void test_trace_block(const MemberRef &mref_, const r
         cand[3] = has ? (int32_t)s_lo.z : -1; cand[4] = has ? (int32_t)s_lo.w : -1;
         cand[5] = has ? (int32_t)s_hi.x : -1; cand[6] = has ? (int32_t)s_hi.y : -1;
         cand[7] = has ? (int32_t)s_hi.z : -1; cand[8] = has ? (int32_t)s_hi.w : -1;
-        TSTAMP(1);
+        DIAG_SINCE(TRACE, LEVEL ? DIAG_TRACE_L1_RECORD : DIAG_TRACE_L0_RECORD, DIAG_WAVE_LANE0, os_t, B.mirror);
         // (the candidates are GLOBAL ids where the population keeps them -- exact attribution: one that lives on another shard
         // becomes a request to its owner, which rolls with the same key, (candidate, tracer's global id); k_xtrace below)
         const uint32_t tracer = (uint32_t)gid_of(P, i);
@@ -203,7 +191,7 @@ __device__ __forceinline__ void test_trace_block(const MemberRef &mref_, const r
             else
                 trace_accept<LEVEL>(P, B, S, nxt, (uint32_t)cand[q]);
         }
-        TSTAMP(2);
+        DIAG_SINCE(TRACE, LEVEL ? DIAG_TRACE_L1_FLAGS : DIAG_TRACE_L0_FLAGS, DIAG_WAVE_LANE0, os_t, B.mirror);
         // infectees beyond the inline slots (an agent that infected more than REINA_INLINE_INFECTEES others): the linked list --
         // through the infectees' own records, or (exact attribution) through the nodes of the pool
         int32_t sib = over;
@@ -219,7 +207,7 @@ __device__ __forceinline__ void test_trace_block(const MemberRef &mref_, const r
             else if (try_queue(P, B, gid_index(P, g), tracer, dp)) trace_accept<LEVEL>(P, B, S, nxt, gid_index(P, g));
             sib = next;
         }
-        TSTAMP(3);
+        DIAG_SINCE(TRACE, LEVEL ? DIAG_TRACE_L1_OVERFLOW : DIAG_TRACE_L0_OVERFLOW, DIAG_WAVE_LANE0, os_t, B.mirror);
     }
     __syncthreads();
     {   // one allocation per list for the whole workgroup, then coalesced copies out of LDS
@@ -242,12 +230,12 @@ __device__ __forceinline__ void test_trace_block(const MemberRef &mref_, const r
             }
         }
     }
-    OSTAMP(LEVEL == 0 ? 1 : 4);
+    DIAG_LAP(OPEN, LEVEL ? DIAG_OPEN_LEVEL1 : DIAG_OPEN_LEVEL0, DIAG_THREAD0, os_t, B.mirror);
     if (LEVEL == 0) {
         // the day's detections by age: to the side block the day's last launch folds into the counters (no waiting for the
         // opening workgroup's snapshot + zeroing: that wait was 5 us of every contact-tracing day at 10^8 agents)
         if (threadIdx.x < REINA_MAX_AGES && s_det[threadIdx.x]) atomicAdd(&B.control[REINA_L_DET_SIDE + threadIdx.x], s_det[threadIdx.x]);
-        OSTAMP(2);
+        DIAG_LAP(OPEN, DIAG_OPEN_DETECTIONS, DIAG_THREAD0, os_t, B.mirror);
     }
     if (LEVEL == 0 && FOLD == 1) {
         // small populations: the level-0 workgroup that finishes last walks the level-1 list itself
@@ -257,7 +245,7 @@ __device__ __forceinline__ void test_trace_block(const MemberRef &mref_, const r
         if (busy > nbx) busy = nbx;
         if (busy == 1) {
             __syncthreads();   // the only one: its own list writes are visible to itself
-            OSTAMP(3);
+            DIAG_LAP(OPEN, DIAG_OPEN_ARRIVAL, DIAG_THREAD0, os_t, B.mirror);
             test_trace_block<1, X>(mref_, dp, 0, 1, lds);
             return;
         }
@@ -272,7 +260,7 @@ __device__ __forceinline__ void test_trace_block(const MemberRef &mref_, const r
             }
         }
         __syncthreads();
-        OSTAMP(3);
+        DIAG_LAP(OPEN, DIAG_OPEN_ARRIVAL, DIAG_THREAD0, os_t, B.mirror);
         if (s_last) test_trace_block<1, X>(mref_, dp, 0, 1, lds);
     }
     // (Measured dead end, round 3, twice: for a large population, level 1 shared by all the level-0 workgroups of this launch

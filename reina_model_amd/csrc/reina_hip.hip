@@ -224,12 +224,6 @@ extern "C" {
 
 int reina_abi_version(void) { return 7; }
 
-#ifdef REINA_ABLATE
-int reina_debug_ablate(uint32_t bits) {   // diagnostic builds only (tools/ablate_day.py)
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_ablate_dev), &bits, sizeof(bits)) == hipSuccess ? 0 : -1;
-}
-#endif
-
 int reina_build_contact_tables(const double *base, const int32_t *row_page, const int32_t *row_place, uint32_t n_rows,
                                const double *mobility, uint32_t n_mobility, const int32_t *rows_mat,
                                const int32_t *sorted_mat, uint32_t n_ages, uint32_t n_entries, double *totals_out,
@@ -323,6 +317,14 @@ int reina_create(const reina_config_t *cfg, const reina_disease_t *disease, rein
     e->cfg.n_shards = cfg->n_shards ? cfg->n_shards : 1;
     if (e->cfg.n_shards > REINA_MAX_SHARDS || e->cfg.shard_rank >= e->cfg.n_shards)
         return refuse_create(e, "n_shards / shard_rank out of range");
+#ifdef DIAG_ANY   // (a diagnostic build, reina_diag.h: its stamps and rows go to buffers.mirror, a sharded engine's mirror tables)
+    if (e->cfg.n_shards > 1 || cfg->exact_attribution) {
+        char sw[160];
+        diag_switches(sw, sizeof sw);
+        return refuse_create(e, std::string("this library was built with") + sw + ": a diagnostic build runs unsharded engines only "
+                                "(buffers.mirror is its scratch, and a sharded engine keeps the mirror tables there)");
+    }
+#endif
     const uint64_t shard_seed = rp_shard_seed(cfg->seed, e->cfg.shard_rank);
     e->h_params.k0 = (uint32_t)shard_seed;
     e->h_params.k1 = (uint32_t)(shard_seed >> 32);
