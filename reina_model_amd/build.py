@@ -22,7 +22,8 @@ DEPS = SOURCES + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.e
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_vaccination.h'),
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_detection.h'),
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_lineage.h'),
-                  os.path.join(os.path.dirname(HERE), 'include', 'reina_summary.h')]
+                  os.path.join(os.path.dirname(HERE), 'include', 'reina_summary.h'),
+                  os.path.join(os.path.dirname(HERE), 'include', 'reina_params.h')]
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-shared', '-std=c++17', '-ffp-contract=off',
                '-fno-fast-math']
 

@@ -1186,3 +1186,6 @@ int reina_profile_read(reina_engine_t *e, double *scan_ms_total, uint64_t *scan_
 
 // ensemble summaries: bands, sums, peaks and exceedance of the members' histories (include/reina_summary.h): kernels and entry point
 #include "k_summary.inc"
+
+// per-member disease parameters of an engine group (include/reina_params.h): the expanding kernel and entry points
+#include "k_params.inc"

@@ -38,10 +38,12 @@ class Setup:
         self.kw = dict(age_counts=age_counts, device=device, engine_factory=engine_factory, interventions=interventions, ipc=ipc)
         self.snapshot = snapshot
 
-    def context(self, variables, seed):
+    def context(self, variables, seed, disease=None, defer_ipc=False):
         """One member: a Context of `variables`; with a snapshot, restored on the HOST only (its checks and the scenario's
-        state: the engines of all members are brought to it by one launch, restore_group)."""
-        c = simulation.make_context(variables, seed=seed, **self.kw)
+        state: the engines of all members are brought to it by one launch, restore_group).  `disease`: a ready disease block
+        the member's engine is created with (run_parameter_ensemble on a library without reina_params.h); `defer_ipc`: the
+        initial population condition waits for Context.apply_initial_condition (run_parameter_ensemble's device route)."""
+        c = simulation.make_context(variables, seed=seed, disease=disease, defer_ipc=defer_ipc, **self.kw)
         if self.snapshot is not None:
             c.restore(self.snapshot, engine_state=False)
         return c
@@ -323,6 +325,45 @@ def run_policy_ensemble(variables, seeds, days, policy, age_counts=None, device=
         plan = setup.planner(variables, seeds[0]).make_plan(days, policy=policy)
         hist = run_group_plan(ctxs, plan, policy=policy, summary=summary)
     return hist, np.stack([c.policy_levels for c in ctxs]), ctxs
+
+
+def run_parameter_ensemble(variables, thetas, seeds, days, space, summary=None, age_counts=None, device='cuda:0',
+                           engine_factory=None, ipc='auto', interventions=None):
+    """The static case of per-member disease parameters (reina_model_amd/parameters.py): member m runs `days` days of
+    `variables` with seed seeds[m] under row m of `thetas` ([K, P], one column per knob of the parameters.ParameterSpace
+    `space`), all as ONE engine group -- prior-predictive runs, sensitivity sweeps.  On the device the members are made with
+    the scenario's disease and one launch (reina_group_params_set) expands all K rows before day 0; on an engine library
+    without the entry points every member is instead CREATED with parameters.expand_numpy's block.  Both routes leave the
+    same blocks, and every member's Context._disease is its own.  Returns (history[K, days, COUNTER_WORDS], contexts);
+    with `summary` (summary.SummarySpec) the EnsembleSummary in place of the history."""
+    from . import parameters as _par
+    seeds = list(seeds)
+    setup = Setup(age_counts, device, engine_factory, interventions, ipc)
+    planner = setup.planner(variables, seeds[0])
+    base, A, V = planner._disease, planner.nr_ages, planner.nr_variants
+    thetas = np.asarray(thetas, dtype=np.float32).reshape(len(seeds), len(space))
+    blocks = _par.expand_many(base, space, thetas, A, V)
+    plan = planner.make_plan(days)
+    if planner.engine.params_f is None:
+        ctxs = [setup.context(variables, sd, disease=b) for sd, b in zip(seeds, blocks)]
+        return run_group_plan(ctxs, plan, summary=summary), ctxs
+    # (the initial population condition draws durations and severities from the disease: it is applied behind the set, so that
+    # it is drawn under the member's own block as on the other route)
+    ctxs = [setup.context(variables, sd, defer_ipc=True) for sd in seeds]
+    group, _ = group_for(ctxs)
+    try:
+        dev = _par.DeviceParameters(group, base, space)
+        try:
+            dev.set(range(len(seeds)), thetas)
+            for c, b in zip(ctxs, blocks):
+                c._disease = b
+                c.apply_initial_condition()
+            hist = run_group_plan(ctxs, plan, group=group, summary=summary)
+        finally:
+            dev.close()
+    finally:
+        group.close()
+    return hist, ctxs
 
 
 def run_branches(snap, variables, seeds, days, member_variables=None, age_counts=None, device='cuda:0', engine_factory=None,

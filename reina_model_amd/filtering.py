@@ -360,6 +360,12 @@ class FilterResult:
         self.log_evidence = 0.0
         self.logw = np.zeros(len(contexts), dtype=np.float64)
         self.timings = []
+        # a filter that learns disease parameters (particle_filter(..., parameters=space)): the space, the device handle, the
+        # members' log theta (the filter's state) and theta [K, P] (what the engines hold)
+        self.space = None
+        self.device_parameters = None
+        self.log_theta = None
+        self.parameters = None
 
     @property
     def n_particles(self):
@@ -417,14 +423,14 @@ class FilterResult:
         q = [float(x) for x in np.atleast_1d(q)]
         return pd.DataFrame(self.weighted_band(self.totals(attr).astype(np.float64), q), index=self.dates(), columns=q)
 
-    def weighted_band(self, values, q=(0.05, 0.5, 0.95)):
+    def weighted_band(self, values, q=(0.05, 0.5, 0.95), weights=None):
         """[T, len(q)]: per column of `values` [K, T] (float64, one row per final particle) the quantiles under the final
-        weights, by the inverted CDF -- the smallest value at which the cumulated weight reaches q.  Members whose value is
-        not finite are left out of their column and the weights renormalised; a column with no finite value is NaN."""
+        weights (or `weights` [K]), by the inverted CDF -- the smallest value at which the cumulated weight reaches q.  Members
+        whose value is not finite are left out of their column and the weights renormalised; a column with no finite value is NaN."""
         values = np.asarray(values, dtype=np.float64)
         if values.ndim != 2 or values.shape[0] != self.n_particles:
             raise ValueError('weighted_band: values are [n_particles, T]')
-        w = self.weights
+        w = self.weights if weights is None else np.asarray(weights, dtype=np.float64)
         q = [float(x) for x in np.atleast_1d(q)]
         out = np.full((values.shape[1], len(q)), np.nan)
         for d in range(values.shape[1]):
@@ -448,6 +454,41 @@ class FilterResult:
         tot = w.sum(axis=0)
         with np.errstate(divide='ignore', invalid='ignore'):
             return np.where(tot > 0, (np.where(keep, values, 0.0) * w).sum(axis=0) / tot, np.nan)
+
+    # ---- a filter with parameters: the posterior over theta
+
+    def _set_theta(self, log_theta):
+        """the members' log theta: theta of it to all K device blocks by one call, and every Context's disease after it"""
+        self.log_theta = np.asarray(log_theta, dtype=np.float64)
+        self.parameters = self.space.theta_of(self.log_theta)
+        dev = self.device_parameters
+        dev.set(range(self.n_particles), self.parameters)
+        for c, d in zip(self.contexts, dev.expand_many(self.parameters)):
+            c._disease = d
+
+    def _theta_windows(self, name):
+        if self.space is None:
+            raise ValueError('the filter learns no parameters (particle_filter(..., parameters=space))')
+        p = self.space.index(name)
+        from datetime import timedelta
+        ws = [w for w in self.windows if w.get('theta') is not None]
+        index = [self.start_date + timedelta(days=w['start_day'] + w['days'] - 1) for w in ws]
+        return p, ws, index
+
+    def parameter_band(self, name, q=(0.05, 0.5, 0.95)):
+        """By window end date (the window's last day): the quantiles of knob `name` over the particles that ran the window,
+        under that window's pre-resample weights (inverted CDF, weighted_band); a DataFrame, one column per q"""
+        import pandas as pd
+        p, ws, index = self._theta_windows(name)
+        q = [float(x) for x in np.atleast_1d(q)]
+        rows = [self.weighted_band(w['theta'][:, p:p + 1], q, weights=w['weights'])[0] for w in ws]
+        return pd.DataFrame(np.asarray(rows).reshape(len(ws), len(q)), index=index, columns=q)
+
+    def parameter_mean(self, name):
+        """By window end date: the mean of knob `name` under the window's pre-resample weights (a Series)"""
+        import pandas as pd
+        p, ws, index = self._theta_windows(name)
+        return pd.Series([float(np.sum(w['weights'] * w['theta'][:, p])) for w in ws], index=index, name=name)
 
     # ---- a logged filter: the posterior over the logs' reports
 
@@ -534,11 +575,15 @@ class FilterResult:
         hist = ensemble.run_group_plan(self.contexts, plan, group=self.group)
         K = self.n_particles
         self.windows.append(dict(start_day=d0, days=int(days), loglik=np.zeros(K), ess=ess(self.weights),
-                                 ancestors=np.arange(K), resampled=False, history=hist, observed=False))
+                                 ancestors=np.arange(K), resampled=False, history=hist, observed=False,
+                                 theta=None if self.parameters is None else self.parameters.copy(), weights=self.weights))
         return hist
 
     def close(self):
-        """closes the engine group, and a logged filter's log (and course) with it"""
+        """closes the engine group -- the device parameters before it --, and a logged filter's log (and course) with it"""
+        if self.device_parameters is not None:
+            self.device_parameters.close()
+            self.device_parameters = None
         if self.group is not None:
             try:
                 glog = _group_log(self.contexts, self.group)
@@ -554,7 +599,7 @@ class FilterResult:
 
 def particle_filter(variables, n_particles, observations=None, obs_model=None, window=7, days=None, seeds=None,
                     filter_seed=0, ess_threshold=0.5, device='cuda:0', engine_factory=None, age_counts=None, snapshot=None,
-                    comm=None, txlog=False, course=False):
+                    comm=None, txlog=False, course=False, parameters=None, shrinkage=0.98):
     """Bootstrap particle filter of `n_particles` members of the scenario `variables` (seeds[m], default 0 .. K - 1) on
     `observations` (a DataFrame indexed by date, e.g. datasets.get_detected_cases; None: no observations, which is
     run_group_plan of the same seeds).  Windows of `window` days; after each one the members are scored with obs_model
@@ -564,7 +609,21 @@ def particle_filter(variables, n_particles, observations=None, obs_model=None, w
     `txlog`: the group keeps a dated transmission log (txlog.py), begun with the first window (with `snapshot`, the past is
     BEFORE), and every clone carries it (reina_group_txlog_clone); `course`: a clinical course log too (course.py; implies
     txlog).  The logs observe and never steer: histories, ancestors and evidence are those of the unlogged filter.  An engine
-    library without the entry points raises EngineError.  Returns a FilterResult.  Sharded Contexts, K < 2, unknown streams and observations with no date inside the horizon are refused
+    library without the entry points raises EngineError.
+    `parameters` (parameters.ParameterSpace): every particle carries a vector theta of multipliers on the disease block
+    (include/reina_params.h).  theta is drawn from the knobs' priors at the start (after the snapshot's
+    restore: the image is checked against the scenario's disease, the base), follows the particle's ancestor at every resample
+    and is perturbed there by the Liu-West step with `shrinkage` (ParameterSpace.liu_west); between resamples it stays.  The
+    initial population condition is applied when the members are made, BEFORE theta is set: its durations and severities are
+    drawn under the scenario's own disease for every particle (ensemble.run_parameter_ensemble draws it under the member's
+    theta).  One
+    call (reina_group_params_set, queued behind the clone on the same stream) hands all K rows to the device.  Prior draws
+    and perturbations come from a generator of their own, PCG64(SeedSequence([filter_seed, 1])): K x P draws at the start
+    and at every resample; the resampling generator's draws are those of a filter without parameters.  log_evidence is then
+    the evidence of scenario AND prior together.  The result's `parameters` is the final [K, P] table; parameter_band /
+    parameter_mean give the posterior by window; windows[k] gains `theta` (in force during the window) and `weights` (its
+    pre-resample weights).  An engine library without the entry points raises EngineError.
+    Returns a FilterResult.  Sharded Contexts, K < 2, unknown streams and observations with no date inside the horizon are refused
     (ValueError; `comm`, a sharded population's communicator, is accepted only to be refused the same way); a failing
     member raises SimulationFailed."""
     from . import ensemble
@@ -593,6 +652,11 @@ def particle_filter(variables, n_particles, observations=None, obs_model=None, w
     txlog = bool(txlog or course)
     if txlog:
         _rep.entry_points(planner.engine, 'filter_log_f', 'logged-clone', 'reina_filter_log.h')
+    if parameters is not None:
+        _rep.entry_points(planner.engine, 'params_f', 'per-member parameter', 'reina_params.h')
+        parameters.check(planner.nr_ages, planner.nr_variants)
+        if not 0.5 < float(shrinkage) <= 1.0:
+            raise ValueError('particle_filter: shrinkage is in (0.5, 1]')
     start_day = int(planner.day)
     if days is None:
         if observations is not None:
@@ -616,6 +680,12 @@ def particle_filter(variables, n_particles, observations=None, obs_model=None, w
     rng = np.random.Generator(np.random.PCG64(filter_seed))
     try:
         setup.restore_group(group, ctxs)
+        if parameters is not None:
+            from .parameters import DeviceParameters
+            theta_rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([int(filter_seed), 1])))
+            res.space = parameters
+            res.device_parameters = DeviceParameters(group, planner._disease, parameters)
+            res._set_theta(parameters.draw_prior(K, theta_rng))
         day = start_day
         while day < start_day + days:
             n = min(window, start_day + days - day)
@@ -640,9 +710,13 @@ def particle_filter(variables, n_particles, observations=None, obs_model=None, w
             if pairs:
                 clone_group(group, pairs, log=ctxs[0].transmission_log.device if txlog else None)
             t4 = time.perf_counter()
+            theta = None if parameters is None else res.parameters.copy()   # (in force during this window)
+            if parameters is not None and resampled:
+                res._set_theta(parameters.liu_west(res.log_theta, w, anc, theta_rng.standard_normal((K, len(parameters))), shrinkage))
+            t5 = time.perf_counter()
             res.windows.append(dict(start_day=day, days=n, loglik=ll, ess=e, ancestors=anc, resampled=resampled,
-                                    history=hist, observed=scorer is not None))
-            res.timings.append(dict(run=t1 - t0, score=t2 - t1, resample=t3 - t2, clone=t4 - t3, pairs=len(pairs)))
+                                    history=hist, observed=scorer is not None, theta=theta, weights=w))
+            res.timings.append(dict(run=t1 - t0, score=t2 - t1, resample=t3 - t2, clone=t4 - t3, pairs=len(pairs), params=t5 - t4))
             day += n
     except BaseException:
         res.close()

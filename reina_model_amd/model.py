@@ -228,13 +228,16 @@ class Context:
     """MI355X-native agent engine with the reference `Context` protocol (main.pyx:1746-2101)."""
 
     def __init__(self, population_params, healthcare_params, disease_params, start_date,
-                 random_seed=4321, device='cuda:0', engine_factory=None, comm=None, strict=False, policy=None, txlog=False, course=False):
+                 random_seed=4321, device='cuda:0', engine_factory=None, comm=None, strict=False, policy=None, txlog=False, course=False,
+                 disease=None):
         """`comm` (sharding.TorchComm or compatible: .rank, .world, .all_reduce_sum/max) makes this
         Context one shard of a population split over comm.world engine instances; population,
         beds, ICU units and import / vaccination quotas given here are the GLOBAL ones.
         `policy` (policy.Policy): run() and run_plan() take the policy route (reina_model_amd/policy.py).
         `txlog`: keep a dated transmission log from the start (reina_model_amd/txlog.py; start_transmission_log()).
-        `course`: keep a clinical course log too (reina_model_amd/course.py; start_course_log()); implies `txlog`."""
+        `course`: keep a clinical course log too (reina_model_amd/course.py; start_course_log()); implies `txlog`.
+        `disease` (engine.Disease): the engine is created with this ready block instead of the one built from disease_params,
+        which still names the variants (parameters.expand_numpy makes such blocks)."""
         from .sharding import split_count, split_population
         self.comm = comm
         self.strict = bool(strict)   # iterate() raises on the day of a problem (main.pyx:2017-2018)
@@ -265,6 +268,7 @@ class Context:
                             "must provide all_to_all(send, recv), or set comm.attribution = 'mirror' for one all-reduce a day")
         population_params = dict(population_params)
         ipc = population_params.pop('initial_population_condition', None)
+        defer_ipc = population_params.pop('defer_initial_population_condition', False)
 
         ages = population_params['age_structure']
         if hasattr(ages, 'items') and hasattr(ages, 'index'):
@@ -295,8 +299,9 @@ class Context:
         self.age_group_labels = list(population_params['age_groups']['labels'])
         self.age_group_indices = np.asarray(population_params['age_groups']['age_indices'], dtype=np.int64)
 
-        disease, self.variant_names = build_disease_struct(
+        built, self.variant_names = build_disease_struct(
             disease_params, nr_ages, population_params['imported_infection_ages'])
+        disease = built if disease is None else disease
         self._disease = disease
         self._seed = int(random_seed) & 0xFFFFFFFFFFFFFFFF
         self._sample_calls = 0
@@ -396,12 +401,20 @@ class Context:
             if self.attribution == 'exact':
                 self.engine.set_alltoall(self._direct.a2a_ptr, self._direct.comm_ptr)
         # main.pyx:1780-1781: the initial condition is applied last, before any intervention exists
-        if ipc is not None and ipc.has_initial_state():
-            self._set_initial_state(ipc)
+        self._pending_ipc = ipc
+        if not defer_ipc:
+            self.apply_initial_condition()
         if txlog or course:
             self.start_transmission_log()
         if course:
             self.start_course_log()
+
+    def apply_initial_condition(self):
+        """Applies the initial population condition the Context was made with, once: at the end of __init__, or -- made with
+        make_context(..., defer_ipc=True) -- when the caller says so, before the first day."""
+        ipc, self._pending_ipc = self._pending_ipc, None
+        if ipc is not None and ipc.has_initial_state():
+            self._set_initial_state(ipc)
 
     def start_course_log(self):
         """Begin a clinical course log (course.CourseLog, also ctx.course_log): from now on every day that the transmission

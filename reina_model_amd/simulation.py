@@ -54,8 +54,11 @@ def create_disease_params(variables):
 
 def make_context(variables, age_counts=None, seed=None, interventions=None, device='cuda:0',
                  engine_factory=None, comm=None, ipc=None, strict=False, snapshot=None, policy=None, txlog=False,
-                 course=False):
-    """Build a Context the way calc/simulation.py:148-180 does.  `ipc`: an InitialPopulationCondition,
+                 course=False, disease=None, defer_ipc=False):
+    """Build a Context the way calc/simulation.py:148-180 does.  `disease` (engine.Disease): a ready disease block the
+    engine is created with, in place of the one built from the variables (parameters.expand_numpy).  `defer_ipc`: the initial
+    population condition is not applied yet; Context.apply_initial_condition() applies it (it draws from the disease block:
+    ensemble.run_parameter_ensemble sets the member's block first).  `ipc`: an InitialPopulationCondition,
     a dict of its fields, None (no initial condition), or 'auto' = what simulate_individuals passes,
     datasets.get_initial_population_condition(variables) (calc/simulation.py:152).
     `snapshot` (snapshot.Snapshot): the Context continues from it (Context.restore); no initial condition is applied, the
@@ -75,6 +78,7 @@ def make_context(variables, age_counts=None, seed=None, interventions=None, devi
         age_structure=np.asarray(age_counts),
         contacts_per_day=datasets.get_contacts_per_day(variables['country']),
         initial_population_condition=datasets.InitialPopulationCondition(**ipc) if isinstance(ipc, dict) else ipc,
+        defer_initial_population_condition=bool(defer_ipc),
         age_groups=dict(labels=groups, age_indices=[groups.index(x) for x in age_to_group]),
         imported_infection_ages=variables['imported_infection_ages'],
     )
@@ -82,7 +86,7 @@ def make_context(variables, age_counts=None, seed=None, interventions=None, devi
     ctx = model.Context(pop_params, hc, create_disease_params(variables), variables['start_date'],
                         random_seed=variables['random_seed'] if seed is None else seed,
                         device=device, engine_factory=engine_factory, comm=comm, strict=strict, policy=policy,
-                        txlog=bool(txlog) and snapshot is None, course=bool(course) and snapshot is None)
+                        txlog=bool(txlog) and snapshot is None, course=bool(course) and snapshot is None, disease=disease)
     if interventions is None:
         ivs = get_active_interventions(variables)
     else:

@@ -10,6 +10,12 @@ Cases:
              synchronised.
   clone_1e7  K = 16 members of 10^7 agents run 120 days as a group; members 8..15 get the states of members 0..7: the clone
              against the snapshot route on that pair list.
+  --params   (alone; writes profiles/params_bench.json) the HUS case without parameters and with one and four knobs
+             (filtering.particle_filter(..., parameters=...): reina_params.h), by --logged's protocol: every leg in a process
+             of its own, alternating over --rounds rounds, --parent DIR for the parent commit's unlogged leg.  Per leg the
+             filter's wall time per window; of the legs with parameters also `params_ms_per_resample` (the Liu-West step, the
+             K blocks' expansion on the host for the Contexts and the set's issue) and `params_set_ms`, the synchronised
+             reina_group_params_set of all 128 members, median of --reps.
   --logged   (alone; writes profiles/filter_log_bench.json) the HUS case three ways -- unlogged, with the transmission log
              (txlog=True), with log and course (course=True): the filter's wall time per window (synchronised at the end), and,
              after 7 more days, the synchronised clone of the last resample's pair list (reina_group_clone, or
@@ -23,7 +29,7 @@ Cases:
 Bytes of a clone, from the shapes and the recorded-agent counts: per pair 8 B per agent (both hot words), 64 B read + 64 B
 written per agent the source has recorded, 64 B written per agent only the destination has, 4 B per changed hot word, the
 bit-plane words (16 B per tile read and written), the dense blocks and the source's queues; over 6.3 TB/s.
-usage: python tools/filter_bench.py [--quick] [--logged [--parent DIR] [--windows W] [--rounds N]] [--out PATH]"""
+usage: python tools/filter_bench.py [--quick] [--logged | --params [--parent DIR] [--windows W] [--rounds N]] [--out PATH]"""
 import argparse
 import copy
 import json
@@ -192,11 +198,24 @@ def timed_clone(contexts, group, pairs, reps, log):
 
 
 LEGS = {'unlogged': {}, 'txlog': dict(txlog=True), 'course': dict(course=True)}
+LOGGED_LEGS = ('unlogged', 'txlog', 'course')
+PARAMS_LEGS = ('unlogged', 'params1', 'params4')
+
+
+def params_space(n):
+    """the first n of four knobs: the --params legs' parameter space"""
+    from reina_model_amd.parameters import Knob, LogNormal, ParameterSpace
+    knobs = [Knob('beta', 'infectiousness_multiplier', prior=LogNormal(1.0, 0.3), bounds=(0.25, 4.0)),
+             Knob('severe', 'p_severe_given_symptomatic', prior=LogNormal(1.0, 0.2), bounds=(0.25, 4.0)),
+             Knob('sus_old', 'p_susceptibility', ages=(60, 100), prior=LogNormal(1.0, 0.2), bounds=(0.25, 4.0)),
+             Knob('incubation', 'mean_incubation_duration', prior=LogNormal(1.0, 0.1), bounds=(0.5, 2.0))]
+    return ParameterSpace(knobs[:n])
 
 
 def one_leg(leg, K, windows_cap, reps):
-    """one leg of --logged in this process: the HUS filter (wall time, synchronised at the end), 7 more days, the timed clone"""
-    kw = LEGS[leg]
+    """one leg of --logged / --params in this process: the HUS filter (wall time, synchronised at the end), 7 more days, the timed clone"""
+    kw = dict(parameters=params_space(int(leg[6:]))) if leg.startswith('params') else LEGS[leg]
+    logged = bool(kw.get('txlog') or kw.get('course'))
     v = copy.deepcopy(VARIABLE_DEFAULTS)
     obs = datasets.get_detected_cases('HUS')
     model = filtering.ObservationModel({'all_detected': 10.0, 'in_ward': 10.0})
@@ -217,16 +236,24 @@ def one_leg(leg, K, windows_cap, reps):
                 break
         res = dict(leg=leg, agents=r.contexts[0].engine.config.n_agents, days=r.days, windows=len(r.windows),
                    resamples=int(sum(w['resampled'] for w in r.windows)), log_evidence=r.log_evidence, wall_s=wall,
-                   wall_ms_per_window=sum(sum(t[k] for k in ('run', 'score', 'resample', 'clone')) for t in r.timings) * 1e3 / len(r.windows),
+                   wall_ms_per_window=sum(sum(t.get(k, 0.0) for k in ('run', 'score', 'resample', 'clone', 'params')) for t in r.timings) * 1e3 / len(r.windows),
                    median_window_run_ms=float(np.median(run_ms)))
         if pairs:
             r.forecast(7)   # (the destinations differ from their sources again, as they do at a resample)
-            ts = timed_clone(r.contexts, r.group, pairs, reps, r.log if kw else None)
+            ts = timed_clone(r.contexts, r.group, pairs, reps, r.log if logged else None)
             res.update(pairs=len(pairs), clone_ms=float(np.median(ts)), clone_ms_all=ts)
-            if kw:
+            if logged:
                 delta, dense, either = log_clone_bytes(r.contexts, pairs, 'course' in kw)
                 res.update(log_bytes_delta=delta, log_bytes_dense=dense, recorded_in_either=either,
                            log_model_ms_at_6p3=delta / PEAK * 1e3)
+        if leg.startswith('params'):
+            # the synchronised set of all K members (the host mirrors and the launches), and the windows' own share
+            from reina_model_amd.parameters import chunk
+            dev, th = r.device_parameters, r.parameters
+            ms, ts = timed(lambda: dev.set(range(K), th), reps)
+            res.update(knobs=len(r.space), params_set_ms=ms, params_set_ms_all=ts, params_set_launches=-(-K // chunk(len(r.space))),
+                       params_ms_per_resample=float(np.median([t['params'] * 1e3 for t, w in zip(r.timings, r.windows) if w['resampled']] or [0.0])),
+                       final_theta_mean=[float(x) for x in (r.weights[:, None] * r.parameters).sum(axis=0)])
         return res
     finally:
         r.close()
@@ -237,25 +264,29 @@ def spread(xs):
     return dict(median=float(np.median(xs)), min=min(xs), max=max(xs), all=xs)
 
 
-def case_logged(K, windows_cap, reps, parent, rounds, on_round=None):
+def case_logged(K, windows_cap, reps, parent, rounds, on_round=None, leg_names=LOGGED_LEGS, case='logged'):
     """every leg in a process of its own that imports the package of its tree (--leg, --root), the legs alternating round by
     round; `parent` (a built checkout of the parent commit) runs the unlogged leg as `parent_unlogged`"""
     import subprocess
-    legs = [('unlogged', ROOT), ('txlog', ROOT), ('course', ROOT)]
+    legs = [(name, ROOT) for name in leg_names]
     if parent:
         legs = [('parent_unlogged', os.path.abspath(parent))] + legs
     runs = {name: [] for name, _ in legs}
 
     def summary(rounds_done):
-        out = dict(case='hus_k%d_logged' % K, K=K, rounds=rounds_done, legs={})
+        out = dict(case='hus_k%d_%s' % (K, case), K=K, rounds=rounds_done, legs={})
         for name, rs in runs.items():
-            last = {k: x for k, x in rs[-1].items() if k not in ('clone_ms_all', 'leg')}
+            last = {k: x for k, x in rs[-1].items() if k not in ('clone_ms_all', 'params_set_ms_all', 'leg')}
+            if all('params_set_ms' in r for r in rs):
+                last.update(params_set_ms=spread([r['params_set_ms'] for r in rs]), params_set_ms_last_round=rs[-1]['params_set_ms_all'])
             last.update(clone_ms=spread([r['clone_ms'] for r in rs]) if all('clone_ms' in r for r in rs) else None,
                         wall_ms_per_window=spread([r['wall_ms_per_window'] for r in rs]),
                         median_window_run_ms=spread([r['median_window_run_ms'] for r in rs]), wall_s=spread([r['wall_s'] for r in rs]),
                         clone_ms_last_round=rs[-1].get('clone_ms_all'))
             out['legs'][name] = last
-        out['log_evidence_equal_in_every_leg'] = len({r['log_evidence'] for rs in runs.values() for r in rs}) == 1
+        same = [rs for name, rs in runs.items() if not name.startswith('params')]   # (a prior changes the evidence)
+        out['log_evidence_equal_in_every_leg' if len(same) == len(runs) else 'log_evidence_equal_without_parameters'] = \
+            len({r['log_evidence'] for rs in same for r in rs}) == 1
         return out
 
     for rnd in range(rounds):
@@ -265,7 +296,7 @@ def case_logged(K, windows_cap, reps, parent, rounds, on_round=None):
                 cmd += ['--windows', str(windows_cap)]
             out = subprocess.run(cmd, cwd=root, stdout=subprocess.PIPE, text=True, check=True).stdout
             runs[name].append(json.loads([ln for ln in out.splitlines() if ln.startswith('{"leg"')][-1]))
-            print(json.dumps({name: {k: x for k, x in runs[name][-1].items() if k != 'clone_ms_all'}}), flush=True)
+            print(json.dumps({name: {k: x for k, x in runs[name][-1].items() if k not in ('clone_ms_all', 'params_set_ms_all')}}), flush=True)
         if on_round is not None:
             on_round(summary(rnd + 1))   # (what has been measured so far is kept)
     return summary(rounds)
@@ -296,6 +327,7 @@ def main():
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'filter_bench.json'))
     ap.add_argument('--logged', action='store_true', help='the logged legs alone (profiles/filter_log_bench.json)')
+    ap.add_argument('--params', action='store_true', help='the legs with per-particle parameters alone (profiles/params_bench.json)')
     ap.add_argument('--windows', type=int, default=None, help="--logged: so many 7-day windows (default: the case file's span)")
     ap.add_argument('--parent', default=None, help='--logged: a built checkout of the parent commit, for its unlogged leg')
     ap.add_argument('--rounds', type=int, default=3, help='--logged: rounds of the alternating legs')
@@ -305,14 +337,16 @@ def main():
     if a.leg:
         print(json.dumps(one_leg(a.leg, 128, a.windows, a.reps)), flush=True)
         return
-    if a.logged:
-        out = a.out if a.out != ap.get_default('out') else os.path.join(ROOT, 'profiles', 'filter_log_bench.json')
+    if a.logged or a.params:
+        what = 'logged' if a.logged else 'params'
+        out = a.out if a.out != ap.get_default('out') else os.path.join(ROOT, 'profiles', 'filter_log_bench.json' if a.logged else 'params_bench.json')
 
         def write(case):
             with open(out, 'w') as f:
-                json.dump(dict(tool='tools/filter_bench.py --logged', peak_bytes_per_s=PEAK, cases=[case]), f, indent=1)
+                json.dump(dict(tool='tools/filter_bench.py --' + what, peak_bytes_per_s=PEAK, cases=[case]), f, indent=1)
 
-        write(case_logged(128, a.windows, a.reps, a.parent, a.rounds, on_round=write))
+        write(case_logged(128, a.windows, a.reps, a.parent, a.rounds, on_round=write,
+                          leg_names=LOGGED_LEGS if a.logged else PARAMS_LEGS, case=what))
         return
     import torch
     res = dict(device=torch.cuda.get_device_name(0), peak_bytes_per_s=PEAK, cases=[])
