@@ -21,6 +21,7 @@ DEPS = SOURCES + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.e
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_course.h'),
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_vaccination.h'),
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_detection.h'),
+                  os.path.join(os.path.dirname(HERE), 'include', 'reina_regime.h'),
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_lineage.h'),
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_summary.h'),
                   os.path.join(os.path.dirname(HERE), 'include', 'reina_params.h')]

@@ -326,19 +326,28 @@ struct TxlArgs {
 // kernel's arguments filled and the grid of the one launch: four workgroups a compute unit over the tiles (each flushes its LDS
 // tables once).  The launch is the caller's callable, not a parameter: launch_members has to name KERNEL<true> and
 // KERNEL<false>, and a callable also has room for what a report queues between the clearing and its kernel.
+// (in two halves for a report that has more to check behind these: day_report_args queues nothing)
+static int day_report_args(const attachment *l, const char *what, uint32_t max_groups, const uint8_t *age_group, uint32_t n_groups, uint32_t n_days,
+                           const uint64_t *dev_report, TxlArgs *a) {
+    if (int rc = age_group_args(l->e0, age_group, n_groups, max_groups, what, &a->p)) return rc;
+    a->n_days = n_days;
+    if (n_days < 1u || n_days > REINA_MAX_DAYS) return refuse(std::string(what) + ": n_days must be in [1, REINA_MAX_DAYS]");
+    if (!dev_report || (reinterpret_cast<uintptr_t>(dev_report) & 15u)) return refuse(std::string(what) + ": the report must be a 16-byte aligned device buffer");
+    return REINA_OK;
+}
+template <class Launch>
+static int day_report_queue(const attachment *l, size_t words, const TxlArgs &a, uint64_t *dev_report, hipStream_t s, Launch launch) {
+    const uint32_t K = (uint32_t)l->members.size();
+    HIP_CHECK(hipMemsetAsync(dev_report, 0, words * 8u * K, s));
+    const uint32_t grid = member_grid(l->e0->n_cus, K, (a.p.n_agents + REPORT_TILE - 1u) / REPORT_TILE, 4u);
+    return launch(a, grid, K);
+}
 template <class Launch>
 static int day_report(const attachment *l, const char *what, uint32_t max_groups, size_t words, const uint8_t *age_group, uint32_t n_groups, uint32_t n_days,
                       uint64_t *dev_report, hipStream_t s, Launch launch) {
     TxlArgs a;
-    uint32_t grid;
-    if (int rc = age_group_args(l->e0, age_group, n_groups, max_groups, what, &a.p)) return rc;
-    a.n_days = n_days;
-    if (n_days < 1u || n_days > REINA_MAX_DAYS) return refuse(std::string(what) + ": n_days must be in [1, REINA_MAX_DAYS]");
-    if (!dev_report || (reinterpret_cast<uintptr_t>(dev_report) & 15u)) return refuse(std::string(what) + ": the report must be a 16-byte aligned device buffer");
-    const uint32_t K = (uint32_t)l->members.size();
-    HIP_CHECK(hipMemsetAsync(dev_report, 0, words * 8u * K, s));
-    grid = member_grid(l->e0->n_cus, K, (a.p.n_agents + REPORT_TILE - 1u) / REPORT_TILE, 4u);
-    return launch(a, grid, K);
+    if (int rc = day_report_args(l, what, max_groups, age_group, n_groups, n_days, dev_report, &a)) return rc;
+    return day_report_queue(l, words, a, dev_report, s, launch);
 }
 
 // the passes of a forest report (the tree report's, the lineage report's): links, `rounds` of pointer jumping, a tally, a

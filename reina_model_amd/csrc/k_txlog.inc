@@ -198,6 +198,7 @@ struct reina_txlog : attachment {            // (last_day: the last day recorded
     size_t stride = 0;                       // words a member: n_agents rounded up to whole tiles
     bool by_hot = true;                      // k_txlog_day's form (REINA_TXLOG_FORM=log: the log word of every active agent; measurement handle)
     reina_course *course = nullptr;          // attached: the day's launch is k_course_day, which records both
+    uint8_t *d_labels = nullptr;             // [members][REINA_MAX_DAYS]: the labels of a regime report (k_regime.inc), made by the first one
 };
 static int course_launch_day(reina_txlog *l, uint32_t grid, uint32_t day, uint32_t by_hot, hipStream_t s);   // (k_course.inc)
 static void course_detach(reina_course *c);   // (the log goes first: the course refuses from then on)
@@ -205,6 +206,7 @@ static void course_detach(reina_course *c);   // (the log goes first: the course
 static void free_txlog(reina_txlog *l) {
     if (l->course) course_detach(l->course);
     if (l->d_log) (void)hipFree(l->d_log);
+    if (l->d_labels) (void)hipFree(l->d_labels);
     delete l;
 }
 

@@ -1178,6 +1178,9 @@ int reina_profile_read(reina_engine_t *e, double *scan_ms_total, uint64_t *scan_
 // the vaccination report taken of a transmission log (include/reina_vaccination.h): kernel and entry point
 #include "k_vaccination.inc"
 
+// a policy and a log in one run, and the regime report taken of a transmission log (include/reina_regime.h): kernel and entry points
+#include "k_regime.inc"
+
 // the clone of a logged group: the particle filter carries both logs (include/reina_filter_log.h): kernel and entry point
 #include "k_filter_log.inc"
 

@@ -403,16 +403,16 @@ class Engine(Handle):
         self.f = bind_abi(lib, prefix)
         self.alloc = allocator
         # the headers beside reina_hip.h (snapshots, transmission-tree reports, the particle filter's in-group clone, triggered
-        # interventions, the dated transmission log, the clone of a logged group, lineage reports, the clinical course log, the vaccination report, the detection report, ensemble summaries, per-member disease parameters): each bound when the library has it,
+        # interventions, the dated transmission log, the clone of a logged group, lineage reports, the clinical course log, the vaccination report, the detection report, the policy-and-log run with the regime report, ensemble summaries, per-member disease parameters): each bound when the library has it,
         # None otherwise
-        from . import course, detection, filtering, lineage, parameters, policy, snapshot, summary, transmission, txlog, vaccination
+        from . import course, detection, filtering, lineage, parameters, policy, regime, snapshot, summary, transmission, txlog, vaccination
         for attr, bind in (('snap_f', snapshot.bind_snapshot_abi), ('tx_f', transmission.bind_tx_abi),
                            ('params_f', parameters.bind_params_abi),
                            ('filter_f', filtering.bind_filter_abi), ('filter_log_f', filtering.bind_filter_log_abi),
                            ('policy_f', policy.bind_policy_abi),
                            ('txlog_f', txlog.bind_txlog_abi), ('lineage_f', lineage.bind_lineage_abi),
                            ('course_f', course.bind_course_abi), ('vacc_f', vaccination.bind_vacc_abi),
-                           ('detect_f', detection.bind_detect_abi),
+                           ('detect_f', detection.bind_detect_abi), ('regime_f', regime.bind_regime_abi),
                            ('summary_f', summary.bind_summary_abi)):
             setattr(self, attr, bind(lib, prefix))
         self.config = config

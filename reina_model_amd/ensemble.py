@@ -24,7 +24,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import (course as _crs, detection as _det, engine as _eng, lineage as _lin, policy as _pol, reports as _rep, simulation, snapshot as _snap,
+from . import (course as _crs, detection as _det, engine as _eng, lineage as _lin, policy as _pol, regime as _rgm, reports as _rep, simulation, snapshot as _snap,
                summary as _summ, transmission as _tx, txlog as _txl, vaccination as _vac)
 from .dayrun import History, replay_plan
 from .filtering import particle_filter  # noqa: F401  (conditioned ensembles: reina_model_amd/filtering.py)
@@ -118,13 +118,14 @@ def _refuse_group_plan(contexts, plan, record_history, member_plans, policy, txl
     if summary is not None:
         _summ.check_group(summary, contexts, plan, record_history)
     logged = [c.transmission_log is not None for c in contexts]
-    if (txlog or any(logged)) and policy is not None:
-        raise ValueError('run_group_plan: a transmission log and a policy cannot be combined')
     if any(logged) and not all(logged):
         raise ValueError('run_group_plan: some members keep a transmission log and some do not')
     if policy is not None:
         if member_plans is not None:
             raise ValueError('run_group_plan: a policy and member_plans (a sweep) cannot be combined')
+        if (txlog or any(logged)) and contexts and getattr(contexts[0].engine, 'regime_f', None) is None:
+            raise ValueError('run_group_plan: a transmission log and a policy cannot be combined on this engine library (it lacks '
+                             'the combined run of include/reina_regime.h)')
         if plan.get('policy') is not policy or plan.get('policy_banks') is None:
             raise ValueError('run_group_plan: the plan must be made with the policy (make_plan(days, policy=...))')
         for c in contexts:
@@ -148,10 +149,12 @@ def _group_and_log(contexts, group, txlog, course):
 
 
 def _replay_group_plan(contexts, plan, member_plans, group, glog, policy, hist):
-    """The plan's days issued to the group -- through the policy.DevicePolicy of a policy (returned, else None), through the
-    group's log, or to the group itself; a sweep's members get their own tables at every table change."""
+    """The plan's days issued to the group -- through the policy.DevicePolicy of a policy (returned, else None; it records
+    into the group's log when there is one), through the group's log, or to the group itself; a sweep's members get their own
+    tables at every table change."""
     if policy is not None:
         dev = _pol.DevicePolicy(policy, contexts[0].start_date, group=group)
+        dev.log = glog
         replay_plan(plan, dev, hist, lambda si, tables: dev.upload_bank(plan['policy_banks'][si][0]))
         return dev
 
@@ -211,7 +214,8 @@ def run_group_plan(contexts, plan, record_history=True, member_plans=None, group
     `txlog`: every member keeps a dated transmission log (reina_model_amd/txlog.py), recorded by one launch a day for the
     whole group; the members' logs end up on `contexts[m].transmission_log` and share the group's device log, which lives as
     long as they do (and keeps a group made for the run open).  A later call with the same `group` continues them; members that keep logs already are continued
-    whatever `txlog` says.  Not together with a policy.
+    whatever `txlog` says.  Together with a policy: the record launch comes behind every day of the policy run
+    (include/reina_regime.h), and regime_reports(contexts) reports transmission by every member's own levels.
 
     `course`: every member keeps a clinical course log too (reina_model_amd/course.py), attached to the group's transmission
     log and recorded by the same launch; implies `txlog`.  The members' course logs end up on `contexts[m].course_log`
@@ -309,21 +313,27 @@ def _run_threaded(setup, variables, seeds, plan, device, threads):
 
 
 def run_policy_ensemble(variables, seeds, days, policy, age_counts=None, device='cuda:0', engine_factory=None, ipc='auto',
-                        interventions=None, summary=None):
+                        interventions=None, summary=None, txlog=False, course=False):
     """One simulation per seed for `days` days, every member reacting to its own counters under `policy` (policy.Policy), all
     as ONE engine group.  Returns (history[K, days, COUNTER_WORDS], levels[K, days], contexts).  An engine library without the
     policy entry points runs the members one after the other by policy.run_host_driven.  `summary` (summary.SummarySpec): the
-    EnsembleSummary in place of the history."""
+    EnsembleSummary in place of the history.  `txlog` / `course`: every member keeps a dated transmission log / a clinical
+    course log too (run_group_plan; on the host-driven route each member keeps its own in host memory)."""
     seeds = list(seeds)
     setup = Setup(age_counts, device, engine_factory, interventions, ipc)
     ctxs = setup.members(variables, seeds)   # (ahead of the planner: what the members' library can do decides whether there is one)
     if ctxs[0].engine.policy_f is None:
+        for c in ctxs:
+            if txlog or course:
+                c.start_transmission_log()
+            if course:
+                c.start_course_log()
         hist = np.stack([_pol.run_host_driven(c, policy, days) for c in ctxs])
         if summary is not None:
             hist = _summ.summarise(hist, ctxs[0].nr_ages, summary, ctx=ctxs[0], members=seeds)
     else:
         plan = setup.planner(variables, seeds[0]).make_plan(days, policy=policy)
-        hist = run_group_plan(ctxs, plan, policy=policy, summary=summary)
+        hist = run_group_plan(ctxs, plan, policy=policy, summary=summary, txlog=txlog, course=course)
     return hist, np.stack([c.policy_levels for c in ctxs]), ctxs
 
 
@@ -442,6 +452,12 @@ def course_reports(contexts, age_groups=None, n_days=None):
 def vaccination_reports(contexts, age_groups=None, n_days=None):
     """vaccination.VaccinationReport of every context (one launch: reina_vacc_report)"""
     return _rep.reports_of_contexts(_vac.VACCINATION, contexts, age_groups, n_days)
+
+
+def regime_reports(contexts, labels=None, age_groups=None, n_days=None):
+    """regime.RegimeReport of every context (one launch: reina_group_regime_report), each member with labels of its own: one
+    sequence per context, or None for every context's own policy levels (Context.policy_level_by_day)"""
+    return _rgm.report_contexts(contexts, labels, age_groups, n_days)
 
 
 def detection_reports(contexts, age_groups=None, n_days=None):

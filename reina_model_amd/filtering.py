@@ -599,7 +599,7 @@ class FilterResult:
 
 def particle_filter(variables, n_particles, observations=None, obs_model=None, window=7, days=None, seeds=None,
                     filter_seed=0, ess_threshold=0.5, device='cuda:0', engine_factory=None, age_counts=None, snapshot=None,
-                    comm=None, txlog=False, course=False, parameters=None, shrinkage=0.98):
+                    comm=None, txlog=False, course=False, parameters=None, shrinkage=0.98, policy=None):
     """Bootstrap particle filter of `n_particles` members of the scenario `variables` (seeds[m], default 0 .. K - 1) on
     `observations` (a DataFrame indexed by date, e.g. datasets.get_detected_cases; None: no observations, which is
     run_group_plan of the same seeds).  Windows of `window` days; after each one the members are scored with obs_model
@@ -624,12 +624,15 @@ def particle_filter(variables, n_particles, observations=None, obs_model=None, w
     parameter_mean give the posterior by window; windows[k] gains `theta` (in force during the window) and `weights` (its
     pre-resample weights).  An engine library without the entry points raises EngineError.
     Returns a FilterResult.  Sharded Contexts, K < 2, unknown streams and observations with no date inside the horizon are refused
-    (ValueError; `comm`, a sharded population's communicator, is accepted only to be refused the same way); a failing
+    (ValueError; `comm`, a sharded population's communicator, and `policy`, a policy.Policy, are accepted only to be refused the
+    same way); a failing
     member raises SimulationFailed."""
     from . import ensemble
     K = int(n_particles)
     if comm is not None:
         raise ValueError('particle_filter: sharded Contexts are not filtered')
+    if policy is not None:
+        raise ValueError('particle_filter: a policy is refused (a clone does not carry the policy state of its source)')
     if K < 2:
         raise ValueError('particle_filter: at least 2 particles')
     seeds = list(range(K)) if seeds is None else [int(s) for s in seeds]

@@ -243,6 +243,9 @@ class Context:
         self.strict = bool(strict)   # iterate() raises on the day of a problem (main.pyx:2017-2018)
         self.policy = policy
         self.policy_levels = None    # after a policy run: the level in force on each of its days
+        # the level of every day run under a policy so far (policy._finish), -1 where no policy decided the day: what the regime
+        # report (regime.py) takes for its labels
+        self.policy_level_by_day = np.full(_eng.MAX_DAYS, -1, dtype=np.int8)
         self.transmission_log = None  # txlog.TransmissionLog once begun: run(), run_plan() and iterate() record every day
         self.course_log = None        # course.CourseLog once begun: recorded with the transmission log it is attached to
         if policy is not None and comm is not None and (comm.world > 1 or getattr(comm, 'always_collective', False)):
@@ -405,6 +408,11 @@ class Context:
         if not defer_ipc:
             self.apply_initial_condition()
         if txlog or course:
+            # (with a policy the keywords ask for the library's combined run, include/reina_regime.h; a library without it
+            # refuses as it always has -- there the logs are begun on the Context and policy.run_host_driven records them)
+            if policy is not None and getattr(self.engine, 'regime_f', None) is None:
+                raise ValueError('transmission log: a Context with a policy is refused by an engine library without the policy-and-log '
+                                 'run (include/reina_regime.h): begin the log on the Context (start_transmission_log / start_course_log)')
             self.start_transmission_log()
         if course:
             self.start_course_log()
@@ -763,11 +771,13 @@ class Context:
         Returns history[days, COUNTER_WORDS] (row d = counters BEFORE day d ran) as a host array,
         or None; `self.mobility_history[d]` is the mobility factor generate_state() would have
         reported on that day.  With a policy attached (Context(..., policy=p)): the policy route -- k_policy ahead of every day
-        on the GPU, policy.run_host_driven on an engine library without the policy entry points -- which also sets
-        `self.policy_levels`."""
+        on the GPU, policy.run_host_driven on an engine library without the policy entry points or with a log kept in host
+        memory -- which also sets `self.policy_levels` and adds to `self.policy_level_by_day`.  A transmission log and a course
+        log are recorded behind every day on either route."""
         if self.policy is not None:
             from . import policy as _pol
-            if self.engine.policy_f is None:
+            log = self.transmission_log
+            if self.engine.policy_f is None or (log is not None and not log.on_device):
                 return _pol.run_host_driven(self, self.policy, days, record_history)
             return _pol.run_device(self, days, record_history)
         if self.transmission_log is not None and not self.transmission_log.on_device:

@@ -253,12 +253,22 @@ def _first_mobility(ctx, dated, day):
     return carried[1] if carried is not None and carried[0] == day else float(dated)
 
 
+def level_by_day(ctx):
+    """Context.policy_level_by_day: int8[MAX_DAYS], the level of every day the Context has run under a policy, -1 elsewhere"""
+    by_day = getattr(ctx, 'policy_level_by_day', None)
+    if by_day is None:
+        by_day = ctx.policy_level_by_day = np.full(_eng.MAX_DAYS, -1, dtype=np.int8)
+    return by_day
+
+
 def _finish(ctx, first_value, levels, segment_of_day, factors, end_day):
-    """the trace of a policy run onto the Context"""
+    """the trace of a policy run onto the Context: policy_levels and mobility_history are the run's own days, policy_level_by_day
+    accumulates over the runs"""
     levels = np.asarray(levels, dtype=np.int32)
     if len(levels):
         ctx.mobility_history = mobility_trace(first_value, segment_of_day, levels, factors)
         ctx._policy_mobility = (int(end_day), float(factors[segment_of_day[-1]][int(levels[-1])]))
+        level_by_day(ctx)[int(end_day) - len(levels):int(end_day)] = levels
     else:
         ctx.mobility_history = []
     ctx.policy_levels = levels
@@ -289,8 +299,12 @@ def run_host_driven(ctx, policy, days, record_history=True):
     """`days` days under `policy`, the plain way: per day read the counters, step_numpy, upload the level's tables when they
     change, iterate -- one blocking round trip a day, on any engine.  Returns history like Context.run and sets
     ctx.policy_levels / ctx.mobility_history.  The policy's state stays with the Context (ctx._policy_state): further calls
-    continue it."""
+    continue it.  A transmission log the Context keeps in host memory, and its course log, are recorded behind every day
+    (txlog.record_numpy / CourseLog.record_host, as txlog.run_host_driven does): the specification of the logged policy run."""
     check_capable(ctx)
+    log = ctx.transmission_log
+    if log is not None and log.on_device:
+        raise ValueError('run_host_driven: this Context keeps its log on the device')
     state = getattr(ctx, '_policy_state', None)
     if state is None or state['policy'] is not policy:
         state = ctx._policy_state = policy.new_state(ctx.start_date)
@@ -313,6 +327,8 @@ def run_host_driven(ctx, policy, days, record_history=True):
             in_force = level
         ctx.engine.step_day(d)
         ctx.day += 1
+        if log is not None:
+            log.record_day(d.day)
         levels.append(level)
         seg_of_day.append(len(factors) - 1)
     _finish(ctx, first_value, levels, seg_of_day, factors, ctx.day)
@@ -349,6 +365,7 @@ class DevicePolicy(_eng.Handle):
         else:
             owner._check(self.f['group_policy_create'](group._h, ctypes.byref(rule), ctypes.byref(self._h)), 'group_policy_create')
         self.policy = policy
+        self.log = None   # the txlog.DeviceLog of the same engine / group, when its days are to be recorded (run_day_array)
 
     def upload_bank(self, tables):
         for level, tab in enumerate(tables):
@@ -356,12 +373,19 @@ class DevicePolicy(_eng.Handle):
             self.owner._check(self.f['policy_upload_level'](self._h, level, ctypes.byref(t), self.alloc.stream()), 'policy_upload_level')
 
     def run_day_array(self, arr, n, history):
-        """history: a device pointer (one engine) or one per member (a group), or None"""
+        """history: a device pointer (one engine) or one per member (a group), or None.  With a device log (self.log): the
+        combined entry points of include/reina_regime.h, the log's record launch behind every day."""
+        f, head, tail = self.f, (self._h,), 'policy_run_days'
+        if self.log is not None:
+            f = _regime_entry_points(self.owner)
+            head, tail = (self._h, self.log._h), 'policy_txlog_run_days'
         if self._grouped:
             hp = _eng.member_pointers(self.group.engines, history)
-            self.owner._check(self.f['group_policy_run_days'](self._h, arr, n, hp, self.alloc.stream()), 'group_policy_run_days')
+            self.owner._check(f['group_' + tail](*head, arr, n, hp, self.alloc.stream()), 'group_' + tail)
         else:
-            self.owner._check(self.f['policy_run_days'](self._h, arr, n, history, self.alloc.stream()), 'policy_run_days')
+            if self.log is not None:
+                self.log._touch()
+            self.owner._check(f[tail](*head, arr, n, history, self.alloc.stream()), tail)
 
     def read_trace(self, first_day, days):
         """[members, days, 2] (level in force, signal); waits for the stream"""
@@ -377,10 +401,22 @@ def plan_segments_of_days(plan):
     return out
 
 
+def _regime_entry_points(engine):
+    from . import reports as _rep
+    return _rep.entry_points(engine, 'regime_f', 'policy-and-log', 'reina_regime.h')
+
+
 def _device_of(ctx):
+    """the Context's DevicePolicy, recording into the Context's own device log when it keeps one (a log in host memory, or a
+    group's, cannot follow the device route)"""
+    log = ctx.transmission_log
+    if log is not None and (log.device is None or log.device.group is not None):
+        raise ValueError('policy: this Context keeps its log %s: the device route cannot record it'
+                         % ('in host memory (policy.run_host_driven runs its days)' if log.device is None else "with its group's"))
     dev = getattr(ctx, '_policy_device', None)
     if dev is None or dev.policy is not ctx.policy:
         dev = ctx._policy_device = DevicePolicy(ctx.policy, ctx.start_date, engine=ctx.engine)
+    dev.log = None if log is None else log.device
     return dev
 
 

@@ -184,8 +184,10 @@ def device_words(engine, f, name, head, members, words, scratch_bytes=None, stal
 #   scratch      (n_agents) -> scratch bytes per member, None without scratch
 #   unconverged  the index of the word that asks for the deep pass (with_deep_pass: max_depth follows the params); None without
 #   extra        (ctx, table) -> further arguments of `report`, the same for every member
-Kind = collections.namedtuple('Kind', 'name of arguments numpy report words names on entry scratch unconverged extra',
-                              defaults=(lambda glog: glog, None, None, None, None))
+#   arrays       how many of the LAST params are host arrays with one row per member (the regime report's labels): the entry
+#                point takes each as a pointer behind the integer params, `report` and `numpy` get a member's own row
+Kind = collections.namedtuple('Kind', 'name of arguments numpy report words names on entry scratch unconverged extra arrays',
+                              defaults=(lambda glog: glog, None, None, None, None, 0))
 
 
 def group_log(contexts):
@@ -219,9 +221,23 @@ def _taken(kind, take, n_agents):
     return take(None) if kind.unconverged is None else with_deep_pass(take, kind.unconverged, n_agents)
 
 
+def _split(kind, params):
+    """(the integer params, the arrays by member) of a kind's params"""
+    params = tuple(params)
+    cut = len(params) - kind.arrays
+    return params[:cut], params[cut:]
+
+
+def _member_params(kind, params, m):
+    """the params as member m's report takes them: of every array its own row"""
+    ints, arrays = _split(kind, params)
+    return ints + tuple(a[m] for a in arrays)
+
+
 def _made(kind, w, contexts, table, labels, params):
     extra = kind.extra(contexts[0], table) if kind.extra is not None else ()
-    return [kind.report(r, *params, len(labels), labels, c.start_date, *extra) for r, c in zip(member_rows(w), contexts)]
+    return [kind.report(r, *_member_params(kind, params, m), len(labels), labels, c.start_date, *extra)
+            for m, (r, c) in enumerate(zip(member_rows(w), contexts))]
 
 
 def device_take(kind, dev, table, n_groups, params):
@@ -230,8 +246,13 @@ def device_take(kind, dev, table, n_groups, params):
     f = dev.f if kind.entry is None else entry_points(e, *kind.entry)
     group = dev.group is not None
     depth = (lambda d: (int(d or 0),)) if kind.unconverged is not None else (lambda d: ())
+    ints, arrays = _split(kind, params)
+    arrays = [np.ascontiguousarray(a) for a in arrays]   # (alive as long as the callable: the entry point reads them where they are)
+    if any(len(a) != dev.members for a in arrays):
+        raise ValueError('%s: one row per member is wanted' % kind.name)
     return lambda d=None: device_words(
-        e, f, kind.names[group], (dev._h, table.ctypes.data, int(n_groups)) + tuple(int(p) for p in params) + depth(d), dev.members,
+        e, f, kind.names[group], (dev._h, table.ctypes.data, int(n_groups)) + tuple(int(p) for p in ints) + depth(d) +
+        tuple(ctypes.c_void_p(a.ctypes.data) for a in arrays), dev.members,
         kind.words(*params), kind.scratch(e.config.n_agents) if kind.scratch is not None else None, dev.engines, group)
 
 
@@ -253,7 +274,7 @@ def report_of(kind, log, *args):
     if _launches(kind, dev) and dev.group is None:
         return reports_of_device(kind, dev, [ctx], *args)[0]
     table, labels, *params = kind.arguments(ctx, *args)
-    take = kind.numpy(ctx, log, table, params)
+    take = kind.numpy(ctx, log, table, _member_params(kind, params, 0))
     w = _taken(kind, lambda depth: take(depth)[None], ctx.engine.config.n_agents)
     return _made(kind, w, [ctx], table, labels, params)[0]
 

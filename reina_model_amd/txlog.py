@@ -23,6 +23,7 @@ library without the log's entry points takes.
 
 In line lists, -1 stands for NONE and -2 for BEFORE.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -120,6 +121,30 @@ def record_numpy(log, hot, day):
     return ons << 16 | inf
 
 
+LinkDays = collections.namedtuple('LinkDays', 'idx s linked bad w v t o tk ok ts os tsk osk both phase')
+
+
+def link_days(hot, infector, log):
+    """The ONE statement of what the reports of a log read of every infected agent (over idx, reports.links): its hot word w and
+    variant v, its infection and onset day t / o (tk / ok: known), its infector's ts / os on a link (tsk / osk: linked and
+    known), both (t and ts known) and the link phase -- 0 t < os, both known (presymptomatic); 1 t >= os, both known; 2 t known
+    and os NONE; 3 anything else.  report_numpy and regime.report_numpy are built on it."""
+    hot = np.asarray(hot).view(np.uint32).ravel()
+    log = np.asarray(log, dtype=np.uint32).ravel()
+    _, idx, s, _, linked, bad = _rep.links(hot, infector)
+    w = hot[idx]
+    v = ((w >> 8) & 3).astype(np.int64)
+    t = (log[idx] & 0xFFFF).astype(np.int64)
+    o = (log[idx] >> 16).astype(np.int64)
+    tk, ok = t < BEFORE, o < BEFORE
+    sl = np.zeros(len(idx), dtype=np.uint32)
+    sl[linked] = log[s[linked]]
+    ts, os_ = (sl & 0xFFFF).astype(np.int64), (sl >> 16).astype(np.int64)
+    tsk, osk = linked & (ts < BEFORE), linked & (os_ < BEFORE)
+    phase = np.where(tk & osk, np.where(t < os_, 0, 1), np.where(tk & (os_ == NONE), 2, 3))
+    return LinkDays(idx, s, linked, bad, w, v, t, o, tk, ok, ts, os_, tsk, osk, tk & tsk, phase)
+
+
 def report_numpy(hot, infector, n_infected, log, age_start, age_group, n_days):
     """The report of one state and its log (the specification of reina_txlog_report).  hot: uint32[N]; infector, n_infected:
     int32[N] (the cold record's fields); log: uint32[N]; age_start: first agent of each age ([A] = N, padded with N);
@@ -127,30 +152,18 @@ def report_numpy(hot, infector, n_infected, log, age_start, age_group, n_days):
     hot = np.asarray(hot).view(np.uint32).ravel()
     n_days = check_n_days(n_days)
     cnt = np.asarray(n_infected).view(np.uint32).ravel().astype(np.uint64)
-    log = np.asarray(log, dtype=np.uint32).ravel()
     table, n_groups, _, age_of = _rep.age_lookup(age_start, age_group)
     words = np.zeros(report_words(n_days), dtype=np.uint64)
-    _, idx, s, _, linked, bad = _rep.links(hot, infector)
-    w = hot[idx]
-    v = ((w >> 8) & 3).astype(np.int64)
-    t = (log[idx] & 0xFFFF).astype(np.int64)
-    o = (log[idx] >> 16).astype(np.int64)
-    tk, ok = t < BEFORE, o < BEFORE
+    idx, s, linked, bad, w, v, t, o, tk, ok, ts, os_, tsk, osk, both, phase = link_days(hot, infector, log)
 
     def hist(offset, bins, sel, value):
         cell = v[sel] * bins + np.clip(value, 0, bins - 1)
         words[offset:offset + VARIANTS * bins] = np.bincount(cell, minlength=VARIANTS * bins).astype(np.uint64)
 
     hist(INCUBATION, INCUBATION_BINS, tk & ok, (o - t)[tk & ok])
-    sl = np.zeros(len(idx), dtype=np.uint32)
-    sl[linked] = log[s[linked]]
-    ts, os_ = (sl & 0xFFFF).astype(np.int64), (sl >> 16).astype(np.int64)
-    tsk, osk = linked & (ts < BEFORE), linked & (os_ < BEFORE)
-    both = tk & tsk
     hist(GENERATION, GENERATION_BINS, both, (t - ts)[both])
     hist(SERIAL, SERIAL_BINS, ok & osk, (o - os_ + SERIAL_SHIFT)[ok & osk])
     hist(TOST, TOST_BINS, tk & osk, (t - os_ + TOST_SHIFT)[tk & osk])
-    phase = np.where(tk & osk, np.where(t < os_, 0, 1), np.where(tk & (os_ == NONE), 2, 3))
     hist(LINK_PHASE, PHASES, linked, phase[linked])
 
     g = table[age_of(idx)].astype(np.int64)
@@ -282,8 +295,6 @@ def check_capable(ctx):
     if ctx.n_shards != 1 or ctx.always_collective:
         raise ValueError('transmission log: sharded Contexts are refused (links are global ids, and a shard sees only its own '
                          "agents' onsets)")
-    if ctx.policy is not None:
-        raise ValueError('transmission log: a Context with a policy is refused (the policy route runs its own days)')
 
 
 def _host_array(t):
@@ -352,7 +363,10 @@ class TransmissionLog:
         self.course = None   # course.CourseLog once one is attached (Context.start_course_log)
         self.device, self._words = device, None
         if device is None:
-            if not host and _eng.is_device(ctx.engine) and ctx.engine.txlog_f is not None:
+            # (under a policy the device log needs the combined run of include/reina_regime.h: a library with the log's entry
+            # points but without those keeps the log in host memory, where policy.run_host_driven records it)
+            combined = ctx.policy is None or getattr(ctx.engine, 'regime_f', None) is not None
+            if not host and _eng.is_device(ctx.engine) and ctx.engine.txlog_f is not None and combined:
                 self.device = DeviceLog(ctx.engine)
             else:
                 self._words = begin_numpy(_host_array(ctx.engine.tensors['hot']))
@@ -404,6 +418,16 @@ class TransmissionLog:
         on host copies otherwise.  Reads the engine's state and the log only."""
         from . import lineage as _lin
         return _lin.report_log(self, period, n_periods, age_groups)
+
+    def regime_report(self, labels=None, age_groups=None, n_days=None):
+        """regime.RegimeReport: transmission by the regime in force -- intervals, presymptomatic share, age mixing, offspring
+        and the links that cross a change, per regime.  labels: day -> regime 0..7 or 0xFF (regime.py), one per day of
+        [0, n_days) (default: the days run so far); None takes the levels of the Context's policy runs
+        (Context.policy_level_by_day; ValueError for a Context that never ran under one).  On the device when the library has
+        the entry points and the log is there, regime.report_numpy on host copies otherwise.  Reads the engine's state and the
+        log only."""
+        from . import regime as _rgm
+        return _rgm.report_log(self, labels, age_groups, n_days)
 
     def vaccination_report(self, age_groups=None, n_days=None):
         """vaccination.VaccinationReport of the days [0, n_days) (default: the days run so far): coverage by date and age group,
