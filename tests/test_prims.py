@@ -97,13 +97,21 @@ def test_inverse_normal_accuracy_and_symmetry(L):
     assert np.array_equal(y[tails], -yc[tails])
 
 
-@pytest.mark.parametrize('mu,cv', [(5.1, 0.86), (21.0, 0.45), (18.8, 0.45)])
+GAMMA_BUNDLED = [(5.1, 0.86), (21.0, 0.45), (18.8, 0.45)]
+# the means a per-member disease block hands the draw (reina_model_amd/parameters.py): float32(base) * float32(theta), one
+# rounding, over the default knob bounds (1e-3, 1e3) -- tests/test_prims_gpu.py runs the same grid on the device
+GAMMA_GRID = [pytest.param(float(np.float32(base) * np.float32(theta)), cv, id='%gx%g-%g' % (base, theta, cv))
+              for base, cv in GAMMA_BUNDLED for theta in (1e-3, 0.05, 0.37, 3, 12, 1e3)]
+
+
+@pytest.mark.parametrize('mu,cv', GAMMA_BUNDLED + GAMMA_GRID)
 def test_gamma_moments(L, mu, cv):
     g = np.zeros(400000, dtype=np.float32)
     L.par_test_gamma(mu, cv, 99, 3, 3, g.ctypes.data, len(g))
+    print('mu %g cv %g: mean error %.4f cv error %.4f' % (mu, cv, abs(g.mean() - mu) / mu, abs(g.std() / g.mean() - cv)))
     assert abs(g.mean() - mu) < 0.01 * mu
     assert abs(g.std() / g.mean() - cv) < 0.01
-    assert g.min() > 0
+    assert g.min() > 0 and np.all(np.isfinite(g))
 
 
 def test_gamma_matches_reference_distribution(L):

@@ -13,6 +13,7 @@ import pytest
 
 import par_backend
 from reina_model_amd import engine as eng
+from test_prims import GAMMA_BUNDLED, GAMMA_GRID
 
 pytestmark = pytest.mark.gpu
 
@@ -77,8 +78,9 @@ def test_expf_logf_on_the_device(dev, host):
     assert np.max(np.abs(d.view(np.float32) - np.log(x.astype(np.float64)))) < 4e-6
 
 
-@pytest.mark.parametrize('mu,cv', [(5.1, 0.86), (21.0, 0.45), (18.8, 0.45)])
+@pytest.mark.parametrize('mu,cv', GAMMA_BUNDLED + GAMMA_GRID)
 def test_gamma_on_the_device(dev, host, mu, cv):
+    """the bundled means, and the grid float32(base) * float32(theta) a per-member disease block hands the draw"""
     n = 400000
     rec = np.zeros((n, 8), dtype=np.uint32)
     rec[:, 0], rec[:, 1] = _bits([mu])[0], _bits([cv])[0]
@@ -88,7 +90,7 @@ def test_gamma_on_the_device(dev, host, mu, cv):
     d = eng.test_prims(dev, 'gamma', rec)[:, 0]
     assert np.array_equal(d, eng.test_prims(host, 'gamma', rec)[:, 0])   # rejection loops and all
     g = d.view(np.float32)
-    assert abs(g.mean() - mu) < 0.01 * mu and abs(g.std() / g.mean() - cv) < 0.01 and g.min() > 0
+    assert abs(g.mean() - mu) < 0.01 * mu and abs(g.std() / g.mean() - cv) < 0.01 and g.min() > 0 and np.all(np.isfinite(g))
 
 
 def test_contact_count_draw_on_the_device(dev, host):
